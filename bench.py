@@ -8,14 +8,20 @@ one "step" = 1000 generations over the whole field (the C3 job).  At N > 1 the
 same field is split into N row stripes, one per GPU and process, with k-deep
 RCCL halo exchanges (strong scaling: total work fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Timed region: W untimed steps, then barrier + device sync, K steps, device sync
-+ barrier; max over ranks.  No HIP events are recorded inside it (r06); K more
-steps with sampled launch events follow it and give the launch durations
-(`roofline`) and the per-rank breakdown.  The field is resident in HBM
-throughout.  Rank 0 prints one JSON line.
++ barrier; max over ranks.  No HIP events are recorded inside it (r06).  The
+field is resident in HBM throughout.  Rank 0 prints one JSON line.
+
+A plain run does only that: create the engine, W + K steps, the line (`value`,
+`ms_per_step`, `config`; the keys --full fills are null).  `--dump-outputs DIR` writes
+what the K-th timed step left on the GPU, as float arrays (dump_outputs).
+`--full` adds everything that takes runs of its own: K more steps with sampled
+launch events, which give the launch durations (`roofline`) and the per-rank
+breakdown, `sub_records`, `cpu_baseline` and, at N > 1, `rccl_selfcheck` and the
+forced `exchange_modes`.
 
 `roofline` names the bound that binds.  The stencil kernel is temporally blocked
 (K = 16 generations per launch) and VALU-issue bound, not HBM bound (DESIGN.md
@@ -86,9 +92,15 @@ def parse():
     p.add_argument("--streams", type=int, default=0)
     p.add_argument("--rule", default="ref", choices=["ref", "conway"])
     p.add_argument("--seed", type=int, default=1)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also the event pass (roofline, per-rank breakdown), sub_records, "
+                        "cpu_baseline and, at N > 1, rccl_selfcheck and the forced exchange modes")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the field the last timed step left as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
     p.add_argument("--no-sub-records", action="store_true",
-                   help="skip the B3/S23 65536^2 and C2 4096^2 lines after the headline")
+                   help="with --full: skip the B3/S23 65536^2 and C2 4096^2 lines after the "
+                        "headline")
     p.add_argument("--cpu-threads", type=int, default=0, help="0 = the allowed CPUs")
     return p.parse_args()
 
@@ -286,13 +298,16 @@ def rccl_selfcheck(pkg, dist, torch, world, rank, local, handoff=0):
     return rec
 
 
-def timed_steps(eng, gens, steps, warmup, world, dist, torch, timing_every=8):
+def timed_steps(eng, gens, steps, warmup, world, dist, torch, timing_every=8, events=True,
+                after_timed=None):
     """W untimed steps, then K steps between barrier + device sync brackets with
     no events on the streams (single-stream engines replay their hipGraph): the
-    measured time.  Then K more steps with HIP events around every
+    measured time.  `after_timed()` then sees the field the K-th step left.  Then
+    (`events`, the --full run) K more steps with HIP events around every
     `timing_every`-th launch (and, on rank engines, every halo round and
     exchange): the launch durations and the per-rank breakdown.  Returns
-    (seconds, seconds of the event pass, timing of the event pass)."""
+    (seconds, seconds of the event pass, timing of the event pass), the last two
+    None without the event pass."""
     def barrier():
         if world > 1:
             dist.barrier()
@@ -312,6 +327,10 @@ def timed_steps(eng, gens, steps, warmup, world, dist, torch, timing_every=8):
     eng.sync()
     eng.set_timing(0)
     dt = region()
+    if after_timed is not None:
+        after_timed()
+    if not events:
+        return dt, None, None
     eng.set_timing(timing_every)
     eng.reset_timing()
     dt_ev = region()
@@ -398,6 +417,136 @@ def sub_record(pkg, torch, local, size, rule, gens, steps, warmup, seed):
         }
 
 
+DUMP_SAMPLE_BYTES = 48 << 20  # cells_sample.npy; all files together stay under 64 MB
+DUMP_SAMPLE_SEED = 0x601D
+
+
+def dump_sample_rows(h, w):
+    """The field rows cells_sample.npy holds: all of them if they fit in
+    DUMP_SAMPLE_BYTES of float32 cells, else the first, the last and a seeded
+    choice of the rest (the same rows for the same field size, ascending)."""
+    import numpy as np
+    n = max(2, DUMP_SAMPLE_BYTES // (4 * w))
+    if n >= h:
+        return np.arange(h, dtype=np.int64)
+    pick = np.random.default_rng(DUMP_SAMPLE_SEED).choice(h - 2, n - 2, replace=False) + 1
+    return np.sort(np.concatenate(([0, h - 1], pick))).astype(np.int64)
+
+
+def row_population(packed):
+    """Live cells per row of a packed (rows, words) uint64 array, as float64."""
+    import numpy as np
+    lut = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint8)
+    out = np.empty(packed.shape[0], dtype=np.float64)
+    for r0 in range(0, packed.shape[0], 4096):  # bounds the byte-count temporary
+        blk = np.ascontiguousarray(packed[r0:r0 + 4096])
+        out[r0:r0 + blk.shape[0]] = lut[blk.view(np.uint8)].sum(axis=1, dtype=np.int64)
+    return out
+
+
+def dump_outputs(path, eng, h, w, world, rank, dist):
+    """--dump-outputs: what a caller of the timed path holds after its last step,
+    the engine's field read back with gol_store_packed / gol_digest, as float
+    arrays under `path` (rank 0 writes; at N > 1 the ranks' stripes in row order):
+      cells_sample.npy    float32 (len(sample_rows), w): the cells (0 / 1) of the
+                          rows dump_sample_rows names -- the whole field when it
+                          fits, else a fixed seeded sample of its rows
+      sample_rows.npy     float64: those rows' indices in the field
+      row_population.npy  float64 (h,): live cells of every row of the field
+      digest.npy          float64 (5,): gol_digest's live-cell count, then its
+                          64-bit hash in four 16-bit limbs, low limb first
+    Not part of the timed region."""
+    import numpy as np
+    packed = eng.store_packed()
+    live, hsh = eng.digest()
+    idx = dump_sample_rows(h, w)
+    mine = idx[(idx >= eng.row0) & (idx < eng.row0 + eng.rows)] - eng.row0
+    bits = np.unpackbits(np.ascontiguousarray(packed[mine]).view(np.uint8), axis=1,
+                         bitorder="little")[:, :w]  # bit j of word q is column 64q + j
+    part = {"cells": bits.astype(np.float32), "pop": row_population(packed),
+            "digest": (live, hsh)}
+    parts = [part]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, part)
+    if rank != 0:
+        return
+    mask = (1 << 64) - 1
+    live = sum(p["digest"][0] for p in parts)
+    hsh = sum(p["digest"][1] for p in parts) & mask  # the hash is a sum over rows
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "cells_sample.npy"), np.concatenate([p["cells"] for p in parts]))
+    np.save(os.path.join(path, "sample_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "row_population.npy"), np.concatenate([p["pop"] for p in parts]))
+    np.save(os.path.join(path, "digest.npy"),
+            np.array([live] + [(hsh >> (16 * i)) & 0xFFFF for i in range(4)], dtype=np.float64))
+
+
+def roofline_record(a, eng, tm, avg_launch_ms, gcups, n, world):
+    """--full: the `roofline` object (module docstring) from the event pass's timing
+    `tm` and the committed counters of this configuration."""
+    # dominant kernel: the fused stencil (HIP events on each stripe's stream)
+    cg_per_launch = tm["cell_gens"] / max(tm["launches"], 1)
+    # a composite engine (gol_config.streams > 1) runs that many stripe launches
+    # concurrently, each timed on its own stream: per-launch rate x streams
+    streams = max(1, tm.get("streams", 1))
+    launch_s = avg_launch_ms / 1e3
+    peak_slot_rate = SIMDS * SPEC_SLOT_RATE  # wave-instruction slots / s (spec)
+    meas_slot_rate = SIMDS * valu_peak_rate()  # best measured issue rate
+    slots_per_launch = cg_per_launch / CELLS_PER_WAVE_INSTR * ISSUED_SLOTS[a.rule]
+    valu_achieved = slots_per_launch * streams / launch_s
+    cfg_key = {"size": n, "rule": a.rule, "tb_depth": eng.tb_depth, "streams": streams,
+               "n_gpus": world, "rows_per_wave": eng.rows_per_wave, "handoff": eng.handoff}
+    ctr = counters_for(cfg_key) or {}
+    insts = ctr.get("insts_valu_per_launch")
+    traffic = ctr.get("hbm_bytes_per_launch")
+    return {
+        "bound": "valu",
+        "achieved": round(valu_achieved / 1e9, 1),
+        "peak": round(peak_slot_rate / 1e9, 1),
+        "unit": "G VALU issue slots/s (the slots the stage logic issues: v_bitop3 "
+                "1 slot, DPP move and v_alignbit 2 slots)",
+        "frac": round(valu_achieved / peak_slot_rate, 4),
+        # the same rate in the r01-r03 slot unit (24 / 28 per lane group and
+        # generation): normalised throughput, the r04 headline `frac`
+        "frac_vs_r03_slot_unit": round(valu_achieved / peak_slot_rate * STAGE_SLOTS[a.rule]
+                                       / ISSUED_SLOTS[a.rule], 4),
+        "peak_from": "MI355X spec: 1024 SIMD-32 x 2.4 GHz / 2 cycles per wave64 "
+                     "VALU instruction",
+        "peak_measured": round(meas_slot_rate / 1e9, 1),
+        "frac_vs_measured": round(valu_achieved / meas_slot_rate, 4),
+        "peak_measured_from": "profiles/r01/valu_rate.json (v_bitop3, 2 waves/SIMD, best "
+                              "code placement) x 1024 SIMDs",
+        # the stage's instruction mix in a microbenchmark at 2 waves/SIMD
+        "peak_mix_measured": (round(SIMDS * valu_mix_rate() / 1e9, 1)
+                              if valu_mix_rate() else None),
+        "frac_vs_mix": (round(valu_achieved / (SIMDS * valu_mix_rate()), 4)
+                        if valu_mix_rate() else None),
+        "traffic": traffic,
+        "kernel": "life_res_kernel" if eng.resident else "life_tb_kernel",
+        "avg_launch_ms": round(avg_launch_ms, 4),
+        "launches": tm["launches"],
+        "concurrent_streams": streams,
+        "cell_gens_per_launch": cg_per_launch,
+        "work_ratio": round(tm["cell_gens_computed"] / max(tm["cell_gens"], 1), 4),
+        "valu": {
+            "slots_per_word_gen": ISSUED_SLOTS[a.rule],
+            "r03_unit_slots_per_word_gen": STAGE_SLOTS[a.rule],
+            "insts_per_launch": insts,
+            "issue_frac": (round(insts * streams / launch_s / peak_slot_rate, 4)
+                           if insts else None),
+            "issue_frac_vs_measured": (round(insts * streams / launch_s / meas_slot_rate, 4)
+                                       if insts else None),
+            "counters_from": (f"profiles/{ctr.get('source_round', 'r02')}/counters.json "
+                              f"(record {ctr.get('source')}, rows_per_wave "
+                              f"{ctr.get('rows_per_wave')})" if insts else None),
+        },
+        "hbm_equiv_frac": round(BYTES_PER_CELL_GEN * gcups / HBM_PEAK_GBPS, 4),
+        "hbm_measured_frac": (round(traffic * streams / launch_s
+                                    / (HBM_PEAK_GBPS * 1e9), 4) if traffic else None),
+    }
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -452,8 +601,10 @@ def main():
         return float(t.item())
 
     modes = None
+    selfcheck = None
     if world > 1:
         dist.init_process_group("gloo" if rehearsal else "nccl")
+    if world > 1 and a.full:
         selfcheck = rccl_selfcheck(pkg, dist, torch, world, rank, local, kw["handoff"])
         # each exchange mode forced -- overlapped (band launch + RCCL exchange on a
         # side stream beside the interior launch, exchange_overlap = 2) and blocking
@@ -472,27 +623,34 @@ def main():
                            "ms_per_step": round(m_dt / a.steps * 1e3, 3),
                            "halo_depth": eng.halo_depth, "per_rank": m_per}
             eng.close()
+    if world > 1:
         eng = rank_engine(0)
     else:
         eng = pkg.Engine(n, n, streams=a.streams, **kw)
-        selfcheck = None
     eng.init_random(a.seed)
 
-    # the timed region runs without events; a second pass of K steps with HIP
-    # events around every 8th launch (representative launch durations without the
-    # per-event stream cost, ~6 us, on every launch) gives the launch times, the
-    # roofline and the per-rank breakdown
-    dt, dt_ev, tm = timed_steps(eng, a.gens, a.steps, a.warmup, world, dist, torch, 8)
+    def dump():
+        dump_outputs(a.dump_outputs, eng, n, n, world, rank, dist)
+
+    # the timed region runs without events; with --full a second pass of K steps
+    # with HIP events around every 8th launch (representative launch durations
+    # without the per-event stream cost, ~6 us, on every launch) gives the launch
+    # times, the roofline and the per-rank breakdown
+    dt, dt_ev, tm = timed_steps(eng, a.gens, a.steps, a.warmup, world, dist, torch, 8,
+                                events=a.full, after_timed=dump if a.dump_outputs else None)
     per_rank = None
-    if world > 1:
+    if world > 1 and a.full:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, rank_breakdown(eng, tm, dt_ev, a.steps, rank))
-    dt_ev = max_over_ranks(dt_ev)
     dt = max_over_ranks(dt)
-    avg_launch_ms = max_over_ranks(tm["kernel_ms"] / max(tm["launches"], 1))
 
     cell_gens = float(n) * n * a.gens * a.steps
     gcups = cell_gens / dt / 1e9
+    roofline = None
+    if a.full:
+        dt_ev = max_over_ranks(dt_ev)
+        avg_launch_ms = max_over_ranks(tm["kernel_ms"] / max(tm["launches"], 1))
+        roofline = roofline_record(a, eng, tm, avg_launch_ms, gcups, n, world)
     if modes is not None:
         mode, tb, to = eng.exchange
         modes["auto"] = {"value": round(gcups, 2), "ms_per_step": round(dt / a.steps * 1e3, 3),
@@ -501,28 +659,13 @@ def main():
                          "tuned_ms_per_round": {"blocking": tb, "overlapped": to},
                          "per_rank": per_rank}
     ok = selfcheck is None or selfcheck.get("ok", True)
-    # dominant kernel: the fused stencil (HIP events on each stripe's stream)
-    cg_per_launch = tm["cell_gens"] / max(tm["launches"], 1)
-    # a composite engine (gol_config.streams > 1) runs that many stripe launches
-    # concurrently, each timed on its own stream: per-launch rate x streams
-    streams = max(1, tm.get("streams", 1))
-    launch_s = avg_launch_ms / 1e3
-    peak_slot_rate = SIMDS * SPEC_SLOT_RATE  # wave-instruction slots / s (spec)
-    meas_slot_rate = SIMDS * valu_peak_rate()  # best measured issue rate
-    slots_per_launch = cg_per_launch / CELLS_PER_WAVE_INSTR * ISSUED_SLOTS[a.rule]
-    valu_achieved = slots_per_launch * streams / launch_s
-    cfg_key = {"size": n, "rule": a.rule, "tb_depth": eng.tb_depth, "streams": streams,
-               "n_gpus": world, "rows_per_wave": eng.rows_per_wave, "handoff": eng.handoff}
-    ctr = counters_for(cfg_key) or {}
-    insts = ctr.get("insts_valu_per_launch")
-    traffic = ctr.get("hbm_bytes_per_launch")
     tuning = eng.tuning
     eng.close()
 
     # north_star's literal rule (B3/S23) at 65536^2 and the C2 field (4096^2,
     # resident kernel), timed after the headline on rank 0 at N = 1
     subs = None
-    if world == 1 and not a.no_sub_records and n == 65536 and a.gens == 1000:
+    if a.full and world == 1 and not a.no_sub_records and n == 65536 and a.gens == 1000:
         subs = {
             ("conway_65536" if a.rule == "ref" else "ref_65536"): sub_record(pkg, torch, local, 65536,
                                        "conway" if a.rule == "ref" else "ref", 1000, 3, 1, a.seed),
@@ -541,7 +684,8 @@ def main():
             "warmup": a.warmup,
             "ms_per_step": round(dt / a.steps * 1e3, 3),
             # the same K steps with HIP events on the streams (the launch timing pass)
-            "ms_per_step_event_pass": round(dt_ev / a.steps * 1e3, 3),
+            "ms_per_step_event_pass": round(dt_ev / a.steps * 1e3, 3) if a.full else None,
+            "full": a.full,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -568,51 +712,7 @@ def main():
                                       if tuning[1] and tuning[2] else None)},
                 "parallelism": f"row-stripes x{world}" if world > 1 else "single GPU",
             },
-            "roofline": {
-                "bound": "valu",
-                "achieved": round(valu_achieved / 1e9, 1),
-                "peak": round(peak_slot_rate / 1e9, 1),
-                "unit": "G VALU issue slots/s (the slots the stage logic issues: v_bitop3 "
-                        "1 slot, DPP move and v_alignbit 2 slots)",
-                "frac": round(valu_achieved / peak_slot_rate, 4),
-                # the same rate in the r01-r03 slot unit (24 / 28 per lane group and
-                # generation): normalised throughput, the r04 headline `frac`
-                "frac_vs_r03_slot_unit": round(valu_achieved / peak_slot_rate * STAGE_SLOTS[a.rule]
-                                               / ISSUED_SLOTS[a.rule], 4),
-                "peak_from": "MI355X_MICROARCH.md: 1024 SIMD-32 x 2.4 GHz / 2 cycles per wave64 "
-                             "VALU instruction",
-                "peak_measured": round(meas_slot_rate / 1e9, 1),
-                "frac_vs_measured": round(valu_achieved / meas_slot_rate, 4),
-                "peak_measured_from": "profiles/r01/valu_rate.json (v_bitop3, 2 waves/SIMD, best "
-                                      "code placement) x 1024 SIMDs",
-                # the stage's instruction mix in a microbenchmark at 2 waves/SIMD
-                "peak_mix_measured": (round(SIMDS * valu_mix_rate() / 1e9, 1)
-                                      if valu_mix_rate() else None),
-                "frac_vs_mix": (round(valu_achieved / (SIMDS * valu_mix_rate()), 4)
-                                if valu_mix_rate() else None),
-                "traffic": traffic,
-                "kernel": "life_res_kernel" if eng.resident else "life_tb_kernel",
-                "avg_launch_ms": round(avg_launch_ms, 4),
-                "launches": tm["launches"],
-                "concurrent_streams": streams,
-                "cell_gens_per_launch": cg_per_launch,
-                "work_ratio": round(tm["cell_gens_computed"] / max(tm["cell_gens"], 1), 4),
-                "valu": {
-                    "slots_per_word_gen": ISSUED_SLOTS[a.rule],
-                    "r03_unit_slots_per_word_gen": STAGE_SLOTS[a.rule],
-                    "insts_per_launch": insts,
-                    "issue_frac": (round(insts * streams / launch_s / peak_slot_rate, 4)
-                                   if insts else None),
-                    "issue_frac_vs_measured": (round(insts * streams / launch_s / meas_slot_rate, 4)
-                                               if insts else None),
-                    "counters_from": (f"profiles/{ctr.get('source_round', 'r02')}/counters.json "
-                                      f"(record {ctr.get('source')}, rows_per_wave "
-                                      f"{ctr.get('rows_per_wave')})" if insts else None),
-                },
-                "hbm_equiv_frac": round(BYTES_PER_CELL_GEN * gcups / HBM_PEAK_GBPS, 4),
-                "hbm_measured_frac": (round(traffic * streams / launch_s
-                                            / (HBM_PEAK_GBPS * 1e9), 4) if traffic else None),
-            },
+            "roofline": roofline,
             "sub_records": subs,
             "cpu_baseline": None,
             "rccl_selfcheck": selfcheck,
@@ -623,7 +723,7 @@ def main():
             rec["rehearsal_classic_blocks"] = shared_gpu
             rec["rehearsal_value"] = round(gcups, 2)
             rec["physical_gpus"] = torch.cuda.device_count()
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(n, a.seed, a.cpu_threads)
         print(json.dumps(rec), flush=True)
     if world > 1:

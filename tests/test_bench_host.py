@@ -102,3 +102,102 @@ def test_timed_steps_has_no_events_in_the_timed_pass():
     assert all(every == 8 for _, every in steps[4:]), steps    # the event pass
     assert tm == {"pass": "events"} and dt > 0 and dt_ev > 0
     assert calls[-1] == ("timing", 0)
+
+
+def test_timed_steps_plain_run_stops_after_the_timed_pass():
+    """events=False (a run without --full): W + K steps and no more, all with
+    timing off, and after_timed sees the engine right after the K-th timed step."""
+    bench = load_bench()
+    calls = []
+
+    class Eng:
+        def step(self, g):
+            calls.append("step")
+
+        def sync(self):
+            pass
+
+        def set_timing(self, every):
+            assert every == 0
+
+        def reset_timing(self):
+            raise AssertionError("no event pass in a plain run")
+
+        timing = reset_timing
+
+    torch = types.SimpleNamespace(cuda=types.SimpleNamespace(synchronize=lambda: None))
+    dt, dt_ev, tm = bench.timed_steps(Eng(), 1000, 5, 2, 1, None, torch, 8, events=False,
+                                      after_timed=lambda: calls.append("dump"))
+    assert calls == ["step"] * 7 + ["dump"]
+    assert dt > 0 and dt_ev is None and tm is None
+    # with the event pass the dump still sits between the two passes
+    calls.clear()
+
+    class EvEng(Eng):
+        def set_timing(self, every):
+            pass
+
+        def reset_timing(self):
+            pass
+
+        def timing(self):
+            return {}
+
+    bench.timed_steps(EvEng(), 1000, 3, 1, 1, None, torch, 8, after_timed=lambda: calls.append("dump"))
+    assert calls == ["step"] * 4 + ["dump"] + ["step"] * 3
+
+
+def test_dump_sample_rows_is_fixed_and_bounded():
+    import numpy as np
+    bench = load_bench()
+    # a field that fits: every row
+    assert (bench.dump_sample_rows(300, 777) == np.arange(300)).all()
+    # the headline field: a seeded sample, the same every time, within the budget
+    h = w = 65536
+    idx = bench.dump_sample_rows(h, w)
+    assert (idx == bench.dump_sample_rows(h, w)).all()
+    assert idx[0] == 0 and idx[-1] == h - 1 and (np.diff(idx) > 0).all()
+    assert len(idx) * w * 4 <= bench.DUMP_SAMPLE_BYTES
+    assert len(idx) * w * 4 + 2 * h * 8 + 5 * 8 + 4 * 128 < 64 << 20  # all four files
+
+
+@pytest.mark.parametrize("world", [1, 3])
+def test_dump_outputs_files(tmp_path, oracle, monkeypatch, world):
+    """dump_outputs on engines that hold an oracle-made field (one engine, or the
+    stripes of 3 ranks gathered in row order): the sampled rows' cells, every
+    row's population and the digest, with a sample budget smaller than the field."""
+    import numpy as np
+    bench = load_bench()
+    h, w = 301, 777
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 40 * 4 * w)
+    field = oracle.bp_run(oracle.bp_random(h, w, 11), w, 2, oracle.CONWAY)
+    cells = np.unpackbits(field.view(np.uint8), axis=1, bitorder="little")[:, :w]
+    bounds = np.linspace(0, h, world + 1).astype(int)
+
+    def engine(r):
+        r0, r1 = bounds[r], bounds[r + 1]
+        # a rank engine hashes its rows at their place in the field (gol_digest)
+        (l0, h0), (l1, h1) = oracle.bp_digest(field[:r0], w), oracle.bp_digest(field[:r1], w)
+        return types.SimpleNamespace(row0=r0, rows=r1 - r0, store_packed=lambda: field[r0:r1],
+                                     digest=lambda: (l1 - l0, (h1 - h0) & ((1 << 64) - 1)))
+
+    parts = []
+
+    class Dist:  # ranks 1.. run first and leave their part; rank 0 gathers them
+        @staticmethod
+        def all_gather_object(out, obj):
+            parts.append(obj)
+            if len(parts) == world:
+                out[:] = parts[-1:] + parts[:-1]
+
+    for r in list(range(1, world)) + [0]:
+        bench.dump_outputs(str(tmp_path), engine(r), h, w, world, r, Dist)
+    idx = bench.dump_sample_rows(h, w)
+    assert len(idx) == 40 and idx[0] == 0 and idx[-1] == h - 1
+    got = np.load(tmp_path / "cells_sample.npy")
+    assert got.dtype == np.float32 and got.shape == (40, w) and (got == cells[idx]).all()
+    assert (np.load(tmp_path / "sample_rows.npy") == idx).all()
+    assert (np.load(tmp_path / "row_population.npy") == cells.sum(axis=1)).all()
+    live, hsh = oracle.bp_digest(field, w)
+    assert np.load(tmp_path / "digest.npy").tolist() == \
+        [live] + [(hsh >> (16 * i)) & 0xFFFF for i in range(4)]

@@ -17,8 +17,8 @@ def test_bench_json_contract():
     n, gens, steps = 2048, 64, 2
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", str(n),
                         "--gens", str(gens), "--steps", str(steps), "--warmup", "1",
-                        "--cpu-threads", "2"], capture_output=True, text=True, timeout=240,
-                       cwd=ROOT)
+                        "--cpu-threads", "2", "--full"], capture_output=True, text=True,
+                       timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -52,8 +52,8 @@ def test_bench_two_rank_rehearsal_exchange_modes():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29561", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                        "--size", "8192", "--gens", "256", "--steps", "2", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
+                        "--size", "8192", "--gens", "256", "--steps", "2", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -67,3 +67,44 @@ def test_bench_two_rank_rehearsal_exchange_modes():
     assert all(v > 0 for v in auto["tuned_ms_per_round"].values())
     for m in modes.values():
         assert m["value"] > 0 and len(m["per_rank"]) == 2
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, oracle):
+    """A plain run (no --full) does the timed steps only: the headline keys are
+    there, what takes runs of its own is null.  --dump-outputs writes the field the
+    last timed step left: (warmup + steps) x gens generations of the seeded field,
+    against the oracle (a width that is no multiple of 64; the field fits the
+    sample budget, so cells_sample.npy is all of it)."""
+    import numpy as np
+    n, gens, steps, warmup, seed = 2000, 64, 2, 1, 3
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size",
+                        str(n), "--gens", str(gens), "--steps", str(steps), "--warmup",
+                        str(warmup), "--seed", str(seed), "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["unit"] == "GCUPS" and rec["higher_is_better"] is True and rec["dtype"] == "u64"
+    assert rec["metric"] and rec["steps"] == steps and rec["warmup"] == warmup
+    assert rec["value"] == pytest.approx(n * n * gens / (rec["ms_per_step"] * 1e-3) / 1e9,
+                                         rel=0.01)
+    assert rec["full"] is False
+    for k in ("roofline", "sub_records", "cpu_baseline", "ms_per_step_event_pass",
+              "rccl_selfcheck", "exchange_modes"):
+        assert rec[k] is None, k
+
+    want = oracle.bp_run(oracle.bp_random(n, n, seed), n, (warmup + steps) * gens, oracle.REF_RULE)
+    cells = np.unpackbits(want.view(np.uint8), axis=1, bitorder="little")[:, :n]
+    assert cells.any(), "the expected field must not be empty"
+    got = {f: np.load(out / f"{f}.npy") for f in ("cells_sample", "sample_rows",
+                                                  "row_population", "digest")}
+    assert sorted(os.listdir(out)) == sorted(f"{f}.npy" for f in got)
+    assert got["cells_sample"].dtype == np.float32
+    assert all(got[f].dtype == np.float64 for f in ("sample_rows", "row_population", "digest"))
+    assert (got["sample_rows"] == np.arange(n)).all()
+    assert got["cells_sample"].shape == (n, n) and (got["cells_sample"] == cells).all()
+    assert (got["row_population"] == cells.sum(axis=1)).all()
+    live, hsh = oracle.bp_digest(want, n)
+    assert got["digest"].tolist() == [live] + [(hsh >> (16 * i)) & 0xFFFF for i in range(4)]

@@ -8,8 +8,9 @@
 # Steps (arguments after ':' are split on spaces):
 #   tests[:FILES]       the -m gpu suite (FILES: test files instead of all of tests/)
 #   smoke               __graft_entry__.smoke()
-#   bench:NAME[:ARGS]   python bench.py ARGS -> NAME.json
-#   rehearse2:NAME[:ARGS]  bench.py --gpus 2 on ONE GPU with self-looped RCCL
+#   bench:NAME[:ARGS]   python bench.py ARGS -> NAME.json (ARGS: --full for the
+#                       roofline, sub_records and cpu_baseline beside the headline)
+#   rehearse2:NAME[:ARGS]  bench.py --gpus 2 --full on ONE GPU with self-looped RCCL
 #                       (GOL_DEV_RCCL_SELF=1, ranks over gloo) -> NAME.json
 #   rehearse8:NAME[:ARGS]  the same with 8 ranks sharing the one GPU
 #   proxy:NAME:ARGS     python tools/rank_proxy.py ARGS -> NAME.jsonl
@@ -47,13 +48,13 @@ for step in "$@"; do
       cut -c1-600 "$OUT/$name.json" ;;
     rehearse2)
       GOL_DEV_RCCL_SELF=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 \
-          --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 \
+          --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full \
           $args > "$OUT/$name.json" 2> "$OUT/$name.err" \
           || { grep -A3 Error "$OUT/$name.err" | head -30; exit 5; }
       cut -c1-600 "$OUT/$name.json" ;;
     rehearse8)
       GOL_DEV_RCCL_SELF=1 timeout -k 10 400 python -u -m torch.distributed.run --nnodes=1 \
-          --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 8 \
+          --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 8 --full \
           $args > "$OUT/$name.json" 2> "$OUT/$name.err" \
           || { grep -A3 Error "$OUT/$name.err" | head -30; exit 5; }
       cut -c1-600 "$OUT/$name.json" ;;

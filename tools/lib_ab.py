@@ -28,9 +28,10 @@ def main():
     for rep in range(a.reps):
         for lib in a.libs.split(","):
             env = dict(os.environ, GOL_LIB=os.path.join(PKG, lib))
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline",
-                                "--no-sub-records"] + extra, env=env, capture_output=True,
-                               text=True, timeout=600)
+            # --full: the event pass behind roofline.avg_launch_ms / frac / work_ratio
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full",
+                                "--no-cpu-baseline", "--no-sub-records"] + extra, env=env,
+                               capture_output=True, text=True, timeout=600)
             if r.returncode != 0:
                 print(r.stderr[-3000:], file=sys.stderr)
                 sys.exit(r.returncode)
