@@ -201,6 +201,18 @@ gol_status gol_set_timing(gol_engine* e, int every);
 gol_status gol_get_timing(gol_engine* e, gol_timing* out);
 gol_status gol_reset_timing(gol_engine* e);
 
+/* Activity skip.  A single-stream engine's classic launches leave out the units
+ * (wavefronts) whose neighbourhood stored nothing new in the two launches before,
+ * within one gol_step: the field is the same, a still region costs almost nothing.
+ * Off on hand-off plans, composite / multi-stream engines, groups, rank engines,
+ * the resident kernel, while gol_set_timing(n > 0) is on, and with
+ * GOL_DEV_ACTIVITY_SKIP=0 in the environment at create.  gol_activity returns how
+ * many units computed and how many skipped a launch, summed over the stencil
+ * launches of gol_step since create or gol_reset_timing (it waits for the
+ * engine's stream).  Either out pointer may be NULL.  Composite engines, group
+ * members and rank engines of more than one rank keep no counters: both are 0. */
+gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units);
+
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */
 gol_status gol_info(gol_engine* e, uint64_t* h, uint64_t* w, uint64_t* row0,
@@ -389,6 +401,19 @@ typedef struct gol_plan_summary {
 } gol_plan_summary;
 gol_status gol_plan_model(uint64_t h, uint64_t w, const gol_config* cfg, int rank, int nranks,
                           int cus, int occ_classic, int occ_hand, gol_plan_summary* out);
+
+/* Host-only, same model: the activity skip's view of the single-stream engine's
+ * launch plan.  Per unit two output rectangles of 4 words each in `rects` (rows
+ * [r0, r1) x 64-column lane groups [q0, q1); r1 <= r0: none; 8 words per unit) and
+ * its neighbour list in CSR form (offsets[units + 1], ids): the units whose
+ * streaks the unit reads before it may skip a launch.  *units and *nids return
+ * the sizes; the arrays are filled only when unit_cap / id_cap hold them (pass 0
+ * and NULLs to ask).  A plan that never skips (hand-off blocks, several segments)
+ * has *nids == 0. */
+gol_status gol_plan_neighbours(uint64_t h, uint64_t w, const gol_config* cfg, int cus,
+                               int occ_classic, int occ_hand, int64_t* rects,
+                               uint32_t* offsets, uint64_t unit_cap, uint32_t* ids,
+                               uint64_t id_cap, uint64_t* units, uint64_t* nids);
 
 /* ---- Multi-GPU (or multi-stripe) inside ONE process, no RCCL ----
  * `nranks` stripe engines of one GLOBAL field (the same partition and halo

@@ -36,7 +36,7 @@ EXPORTS = [
     "gol_create_rank_transport", "gol_round_schedule", "gol_plan_handoff",
     "gol_plan_resident", "gol_plan_skew", "gol_plan_columns", "gol_plan_tuning",
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
-    "gol_plan_resident_rows", "gol_plan_exchange",
+    "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
 ]
 
 # gol_plan_tuning's variants (plan.cpp kTuneVariantNames): 0 = the models' plan
@@ -194,6 +194,9 @@ def lib():
                                      ctypes.POINTER(u32)]
     L.gol_plan_model.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, i32, i32,
                                  ctypes.POINTER(PlanSummary)]
+    L.gol_activity.argtypes = [vp, pu64, pu64]
+    L.gol_plan_neighbours.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, vp, u64,
+                                      vp, u64, pu64, pu64]
     for name in ["gol_create", "gol_create_rank", "gol_load_ascii", "gol_store_ascii",
                  "gol_load_packed", "gol_store_packed", "gol_init_random", "gol_step",
                  "gol_sync", "gol_digest", "gol_set_timing", "gol_get_timing",
@@ -202,7 +205,8 @@ def lib():
                  "gol_plan_resident", "gol_plan_skew", "gol_plan_columns",
                  "gol_create_rank_transport", "gol_round_schedule", "gol_plan_tuning",
                  "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
-                 "gol_plan_resident_rows", "gol_plan_exchange"]:
+                 "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity",
+                 "gol_plan_neighbours"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -268,6 +272,27 @@ def plan_model(h, w, rank=0, nranks=1, cus=256, occ_classic=2, occ_hand=2, **cfg
     _check(lib().gol_plan_model(h, w, ctypes.byref(cfg), rank, nranks, cus, occ_classic,
                                 occ_hand, ctypes.byref(out)))
     return {k: getattr(out, k) for k, _ in PlanSummary._fields_ if k != "reserved"}
+
+
+def plan_neighbours(h, w, cus=256, occ_classic=2, occ_hand=2, **cfg_kw):
+    """gol_plan_neighbours (host only, no GPU): the activity skip's view of the launch
+    plan gol_create would build.  Returns (rects, offsets, ids): rects an int64
+    array [units, 2, 4] of (r0, r1, q0, q1) -- rows [r0, r1) x 64-column lane groups
+    [q0, q1), r1 <= r0: none -- and the units' neighbour lists in CSR form
+    (ids[offsets[u]:offsets[u + 1]]); ids is empty for a plan that never skips."""
+    import numpy as np
+    cfg = make_config(**cfg_kw)
+    nu, ni = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().gol_plan_neighbours(h, w, ctypes.byref(cfg), cus, occ_classic, occ_hand, None,
+                                     None, 0, None, 0, ctypes.byref(nu), ctypes.byref(ni)))
+    rects = np.zeros((nu.value, 2, 4), dtype=np.int64)
+    offs = np.zeros(nu.value + 1, dtype=np.uint32)
+    ids = np.zeros(max(1, ni.value), dtype=np.uint32)
+    _check(lib().gol_plan_neighbours(h, w, ctypes.byref(cfg), cus, occ_classic, occ_hand,
+                                     rects.ctypes.data, offs.ctypes.data, nu.value,
+                                     ids.ctypes.data, ni.value, ctypes.byref(nu),
+                                     ctypes.byref(ni)))
+    return rects, offs, ids[:ni.value]
 
 
 def unique_id() -> bytes:
@@ -427,6 +452,14 @@ class Engine:
 
     def reset_timing(self):
         _check(lib().gol_reset_timing(self._h))
+
+    def activity(self):
+        """(computed, skipped): units (wavefronts) that computed / skipped a stencil
+        launch of step() since create or reset_timing() (gol_activity; waits for
+        the engine's stream)."""
+        c, k = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().gol_activity(self._h, ctypes.byref(c), ctypes.byref(k)))
+        return c.value, k.value
 
     def timing(self):
         t = Timing(struct_size=ctypes.sizeof(Timing))

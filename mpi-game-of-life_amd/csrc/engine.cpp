@@ -277,6 +277,20 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
             e->reg_hand = false;
         }
     }
+    // activity skip: engines of gol_create on one stream (e->act_on so far: the
+    // caller allows it) whose plan has neighbour lists, i.e. classic single-pass
+    // blocks; GOL_DEV_ACTIVITY_SKIP=0 turns it off (A/B runs, tests)
+    {
+        const char* v = std::getenv("GOL_DEV_ACTIVITY_SKIP");
+        // (two field buffers: a skipped unit relies on launch m writing the buffer
+        // launch m - 2 wrote, so an engine that may run multi-pass launches, with
+        // its 4 rotating buffers, never skips, even on a plan that fell back to
+        // single passes; nor one with the dev row shift, whose moved block
+        // boundaries unit_rects does not model)
+        e->act_on = e->act_on && !(v && std::atoi(v) == 0) && !e->res.on && e->d_streak &&
+                    !e->plans.empty() && e->plans[0].d_nb && !e->shared_device && !e->grouped &&
+                    e->nbuf == 2 && e->npass <= 1 && !e->xcd_shift;
+    }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return GOL_OK;
 }
@@ -599,6 +613,24 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     a.pair_units = p.pair_units;
     a.pair0 = p.total_units - p.pair_units;
     a.pairs = p.dpairs;
+    // activity skip: launches of a gol_step of a single-stream engine (step_single
+    // counts them in act_launch; the autotuner's and every other launch: -1).  The
+    // streaks live within one step: its first launch carries no history, the
+    // parity alternates from there, and a launch at another depth (the remainder,
+    // always last) computes everything and leaves the streaks alone.
+    if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
+        a.act = e->d_streak + 2 * e->act_units;
+        if (e->act_on && !e->timing_every && depth == e->K && !hand && passes == 1 && p.d_nb &&
+            p.npass == 1 && e->nbuf == 2 && !a.xcd_shift && p.total_units <= e->act_units) {
+            const int par = e->act_launch & 1;
+            a.streak_in = e->d_streak + (size_t)par * e->act_units;
+            a.streak_out = e->d_streak + (size_t)(par ^ 1) * e->act_units;
+            a.nb_off = p.d_nb;
+            a.nb_ids = p.d_nb + p.nb_off.size();
+            a.no_hist = e->act_launch == 0 ? 1 : 0;
+        }
+        ++e->act_launch;
+    }
 #if GOL_EXP
     a.wlog = g_dev_wave_log;
     a.prog = g_dev_prog;
@@ -753,6 +785,7 @@ gol_status gol_create(uint64_t h, uint64_t w, const gol_config* cfg, gol_engine*
         *out = e;
         return GOL_OK;
     }
+    e->act_on = true;  // (activity skip) allowed; init_common decides
     st = init_common(e, h, w, cfg, nullptr);
     if (st != GOL_OK) {
         std::string msg = g_last_error;
@@ -832,6 +865,47 @@ gol_status gol_plan_model(uint64_t h, uint64_t w, const gol_config* cfg, int ran
     return GOL_OK;
 }
 
+gol_status gol_plan_neighbours(uint64_t h, uint64_t w, const gol_config* cfg, int cus,
+                               int occ_classic, int occ_hand, int64_t* rects, uint32_t* offsets,
+                               uint64_t unit_cap, uint32_t* ids, uint64_t id_cap, uint64_t* units,
+                               uint64_t* nids)
+{
+    if (!units || !nids) return fail(GOL_EINVAL, "null out");
+    *units = *nids = 0;
+    gol_status st = check_cfg(cfg);
+    if (st != GOL_OK) return st;
+    if (h == 0 || w == 0) return fail(GOL_EINVAL, "h and w must be >= 1");
+    if (h > (1ull << 40) || w > (1ull << 40)) return fail(GOL_EINVAL, "field too large");
+    if (cus <= 0 || occ_classic <= 0 || occ_hand < 0)
+        return fail(GOL_EINVAL, "cus and occ_classic must be >= 1, occ_hand >= 0");
+    std::unique_ptr<gol_engine> e(new (std::nothrow) gol_engine());
+    if (!e) return fail(GOL_ENOMEM, "host allocation");
+    e->model.on = true;
+    e->model.cus = cus;
+    e->model.occ_c = occ_classic;
+    e->model.occ_h = occ_hand;
+    e->R = h;
+    GOL_TRY(host_layout(e.get(), h, w, cfg));
+    std::vector<std::vector<SegDesc>> raw;
+    GOL_TRY(raw_regions(e.get(), h, cfg, nullptr, raw));
+    decide_passes(e.get(), (size_t)(e->buf_rows + 2 * gol::kGuardRows) * e->stride);
+    GOL_TRY(build_plans(e.get(), raw));
+    if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
+    const auto& p = e->plans[0];
+    *units = (uint64_t)p.total_units;
+    *nids = p.nb_ids.size();
+    if (rects && unit_cap >= *units) {
+        std::vector<URect> rc;
+        unit_rects(p, (int64_t)e->ng, rc);
+        std::memcpy(rects, rc.data(), rc.size() * sizeof(URect));
+    }
+    if (offsets && ids && unit_cap >= *units && id_cap >= *nids && !p.nb_off.empty()) {
+        std::memcpy(offsets, p.nb_off.data(), p.nb_off.size() * sizeof(uint32_t));
+        std::memcpy(ids, p.nb_ids.data(), p.nb_ids.size() * sizeof(uint32_t));
+    }
+    return GOL_OK;
+}
+
 }  // extern "C"
 
 
@@ -878,6 +952,7 @@ void gol_destroy(gol_engine* e)
         if (e->flags[b]) (void)hipFree(e->flags[b]);
     }
     if (e->mpflags) (void)hipFree(e->mpflags);
+    if (e->d_streak) (void)hipFree(e->d_streak);
     if (e->d_err) (void)hipFree(e->d_err);
     if (e->res.flags) (void)hipFree(e->res.flags);
     for (hipEvent_t ev : {e->res.ev_in, e->res.ev_out})
@@ -1129,9 +1204,21 @@ int passes_for(const gol_engine* e, int plan, uint32_t d, uint64_t left)
 // Single-stream engines: the launch sequence of gol_step(gens) as a captured
 // hipGraph, replayed from the second call on (LRU cache keyed by gens and the
 // starting buffer).
+static gol_status step_single_launches(gol_engine* e, uint64_t generations);
+
 gol_status step_single(gol_engine* e, uint64_t generations)
 {
     if (e->res.on) return step_resident(e, generations);
+    // (activity skip) the launches issued or captured below are one step's: launch()
+    // numbers them from 0
+    e->act_launch = 0;
+    const gol_status st = step_single_launches(e, generations);
+    e->act_launch = -1;
+    return st;
+}
+
+static gol_status step_single_launches(gol_engine* e, uint64_t generations)
+{
     uint64_t left = generations;
     const bool graphable = e->timing_every == 0 && generations >= 4 * (uint64_t)e->K;
     if (graphable) {
@@ -1397,6 +1484,39 @@ gol_status gol_reset_timing(gol_engine* e)
     gol_status st = flush_timing(e);
     if (st != GOL_OK) return st;
     e->tm = gol_timing{};
+    if (e->d_streak) {
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipMemsetAsync(e->d_streak + 2 * e->act_units, 0,
+                               2 * (size_t)e->act_units * sizeof(uint32_t), e->stream));
+    }
+    return GOL_OK;
+}
+
+gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    uint64_t c = 0, k = 0;
+    if (!e->parts.empty()) {
+        for (auto* p : e->parts) {
+            uint64_t pc = 0, pk = 0;
+            gol_status st = gol_activity(p, &pc, &pk);
+            if (st != GOL_OK) return st;
+            c += pc;
+            k += pk;
+        }
+    } else if (e->d_streak) {
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        std::vector<uint32_t> v(2 * (size_t)e->act_units);
+        HIP_TRY(hipMemcpy(v.data(), e->d_streak + 2 * e->act_units, v.size() * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < v.size(); i += 2) {
+            c += v[i];
+            k += v[i + 1];
+        }
+    }
+    if (computed_units) *computed_units = c;
+    if (skipped_units) *skipped_units = k;
     return GOL_OK;
 }
 

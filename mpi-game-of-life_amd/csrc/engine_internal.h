@@ -276,6 +276,10 @@ struct gol_engine {
         std::vector<int64_t> pairs;
         int64_t* dpairs = nullptr;
         SegDesc* dev = nullptr;
+        // activity skip (build_neighbours): the units' neighbour lists, CSR; on the
+        // device the offsets followed by the ids.  Empty: the plan never skips
+        std::vector<uint32_t> nb_off, nb_ids;
+        uint32_t* d_nb = nullptr;
         // a copy of an earlier plan of the same rows (rank engines: the full-depth
         // launches of a round share one plan); its device tables are the owner's
         bool alias = false;
@@ -303,6 +307,17 @@ struct gol_engine {
     uint64_t* side[2] = {nullptr, nullptr};
     uint32_t* flags[2] = {nullptr, nullptr};
     int* d_err = nullptr;
+
+    // Activity skip (life_stencil.h).  d_streak: 2 x act_units streak
+    // words (by launch parity), then 2 x act_units counters (computed, skipped per
+    // unit).  act_on: the engine may skip (decided at create).  act_launch: index of
+    // the next stencil launch within the gol_step that is being issued, -1 outside
+    // one: history never outlives a step, so nothing that touches the field
+    // between steps can leave a stale streak.
+    uint32_t* d_streak = nullptr;
+    int64_t act_units = 0;
+    bool act_on = false;
+    int act_launch = -1;
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on
@@ -380,6 +395,11 @@ gol_status quiesce(gol_engine* e);
 gol_status check_err(gol_engine* e);
 
 // ---- plan.cpp
+struct URect {
+    int64_t r0, r1, q0, q1;  // rows [r0, r1) x lane groups [q0, q1)
+};
+void unit_rects(const gol_engine::Plan& p, int64_t ng, std::vector<URect>& out);
+void build_neighbours(gol_engine::Plan& p, int64_t ng, int K);
 bool handoff_fits(int64_t R, int d, int planes);
 bool single_stream_skews(uint64_t h, uint64_t w, const gol_config* cfg);
 void free_plan(gol_engine::Plan& q);

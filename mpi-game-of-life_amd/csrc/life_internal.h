@@ -111,7 +111,22 @@ struct StepArgs {
     // bits 2x..2x+1 = speed class of blockIdx mod 8 == x, bits 16-23 = strip
     // modulus m; 0 = off
     uint32_t xcd_shift;
+    // Activity skip (classic single-pass launches of one segment at the plan's depth;
+    // life_stencil.h): a unit that stored no word different from the
+    // generation before writes min(streak_in + 1, kStreakCap) to streak_out[unit],
+    // else 0; a unit whose neighbour list nb_ids[nb_off[unit] .. nb_off[unit + 1])
+    // (plan.cpp build_neighbours; it holds the unit itself) has streak_in >= 2
+    // throughout stores no row.  streak_out null = off; no_hist: the first launch
+    // of a step, which ignores streak_in.  act (may be set alone): 2 counters per
+    // unit, launches computed / skipped.
+    const uint32_t* streak_in;
+    uint32_t* streak_out;
+    const uint32_t* nb_off;
+    const uint32_t* nb_ids;
+    uint32_t* act;
+    int32_t no_hist;
 };
+constexpr uint32_t kStreakCap = 255;
 
 // Fused depths with an instantiated kernel, largest first.  The shipped library
 // builds the depths auto_layout and the remainder launches use; the dev build

@@ -166,6 +166,7 @@ constexpr uint32_t kAnd3 = 0x80;      // a & b & c
 constexpr uint32_t kFour = 0x42;      // ~(a ^ b) & (a ^ c)
 constexpr uint32_t kAndNot = 0x40;    // a & b & ~c
 constexpr uint32_t kOrAnd2 = 0xEA;    // (a & b) | c
+constexpr uint32_t kOrXor = 0xF6;     // a | (b ^ c)
 
 // Horizontal neighbours of a lane group x (bitlayout.h).  Plane k's left
 // neighbours are plane k-1 and its right neighbours plane k+1, at the same bit,
@@ -500,6 +501,33 @@ void life_tb_kernel(StepArgs a)
     const int64_t unit =
         (int64_t)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (unit >= a.total_units) return;
+    // Activity skip (classic single-pass blocks; StepArgs::streak_out).
+    // Before any field load: when every unit of the neighbour list (this unit
+    // among them; one list entry per lane) stored nothing new in the two launches
+    // before this one, the rows this unit would store are the ones the output
+    // buffer holds since the launch before last.  Anything else computes.
+    constexpr bool kTrack = !HAND && !MP;
+    uint32_t streak = 0;  // this unit's quiet launches so far (uniform)
+    uint32_t acc = 0;     // OR of (generation K) ^ (generation K - 1) over the rows stored
+    if constexpr (kTrack) {
+        if (a.streak_out && !a.no_hist) {
+            const uint32_t o0 = a.nb_off[unit], o1 = a.nb_off[unit + 1];
+            bool still = o1 > o0;
+            for (uint32_t j = o0; j < o1; j += 64) {
+                const uint32_t i = j + (uint32_t)lane;
+                const uint32_t s = i < o1 ? a.streak_in[a.nb_ids[i]] : 2u;
+                still = still && __builtin_amdgcn_ballot_w64(s < 2u) == 0;
+            }
+            streak = __builtin_amdgcn_readfirstlane(a.streak_in[unit]);
+            if (still) {
+                if (lane == 0) {
+                    a.streak_out[unit] = min(streak + 1u, kStreakCap);
+                    if (a.act) a.act[2 * unit + 1] += 1u;
+                }
+                return;
+            }
+        }
+    }
 #if GOL_EXP & 128
     const uint64_t wl_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1055,8 +1083,20 @@ void life_tb_kernel(StepArgs a)
             for (int p = 0; p < kPrefetch; ++p) {
                 const int g = d - p;
                 if (g >= 0 && g < K && (!kGuard || t0 + p >= 2 * g)) {
+                    // (activity skip) the last stage holds the generation K - 1 cells
+                    // of the row it emits: one v_bitop3 per plane ORs the difference
+                    // into acc, from step 2K on (the rows `store` stores; the steps
+                    // past T emit exact rows of the block below, which can only add
+                    // a spurious "changed")
+                    const bool track = kTrack && g == K - 1 && (!kGuard || t0 + p >= 2 * K);
+                    Pl<NP> was{};
+                    if (track) was = st[g].al;
                     x[p] = stage_rm(g, p, x[p], kMask ? rmv[p - g - 1 + K] : 0u,
                                     std::integral_constant<bool, kMask>{});
+                    if (track) {
+#pragma unroll
+                        for (int k = 0; k < NP; ++k) acc = lop3<kOrXor>(acc, x[p].v[k], was.v[k]);
+                    }
                     if constexpr (HAND && kGuard && !(GOL_EXP & 4)) {
                         if (g <= K - 2 && (t0 + p == 2 * g + 2 || t0 + p == 2 * g + 3))
                             store_side<NP>(reinterpret_cast<uint64_t*>(
@@ -1222,6 +1262,18 @@ void life_tb_kernel(StepArgs a)
         if (done_need) mp_raise(done_flag(pass, unit));
     }
     }  // pass
+    if constexpr (kTrack) {
+        // (activity skip) quiet: no output lane of the unit stored a word that
+        // differs from the generation before (halo lanes and lanes outside the
+        // field hold contaminated values and do not count; st_lane is the store
+        // lambda's st_ok here: kTrack excludes multi-pass blocks, whose halo lanes
+        // also store, to their shadow rows)
+        if (a.streak_out) {
+            const bool changed = __builtin_amdgcn_ballot_w64(st_lane && acc != 0u) != 0;
+            if (lane == 0) a.streak_out[unit] = changed ? 0u : min(streak + 1u, kStreakCap);
+        }
+        if (a.act && lane == 0) a.act[2 * unit] += 1u;
+    }
 #if GOL_EXP & 128
     if (a.wlog && lane == 0) {
         // 8 words per wavefront: start, end, HW_ID | XCC_ID, block | workgroup,

@@ -378,8 +378,108 @@ void free_plan(gol_engine::Plan& q)
     if (q.alias) return;  // the owner's tables
     if (q.dev) (void)hipFree(q.dev);
     if (q.dpairs) (void)hipFree(q.dpairs);
+    if (q.d_nb) (void)hipFree(q.d_nb);
     q.dev = nullptr;
     q.dpairs = nullptr;
+    q.d_nb = nullptr;
+}
+
+// Activity skip (life_stencil.h): the output rectangles of a
+// one-segment plan's units, two per unit (rows [r0, r1) x lane groups [q0, q1);
+// r1 <= r0: none), derived as the kernel derives them.  Row blocks are bottom-up
+// and age-skewed per strip, the half strip packs two row blocks per unit, so the
+// tiles of neighbouring strips do not line up.
+void unit_rects(const gol_engine::Plan& p, int64_t ng, std::vector<URect>& out)
+{
+    out.assign((size_t)(2 * p.total_units), URect{0, 0, 0, 0});
+    if (p.segs.size() != 1) return;
+    const SegDesc& sg = p.segs[0];
+    const int64_t full = p.total_units - p.pair_units, strips = p.groups;
+    const int64_t ry = p.rows_old ? p.rows_young : p.rpw;
+    for (int64_t unit = 0; unit < full; ++unit) {
+        const int64_t s = unit % strips, blk = sg.nblk - 1 - unit / strips;
+        int64_t rb = sg.out_lo + blk * ry, rlen = ry;
+        if (p.rows_old) {
+            const int64_t jo = std::min<int64_t>(
+                sg.nblk, p.units_old > s ? (p.units_old - s + strips - 1) / strips : 0);
+            const int64_t ny = sg.nblk - jo;
+            if (blk >= ny) {
+                rb = sg.out_lo + ny * ry + (blk - ny) * p.rows_old;
+                rlen = p.rows_old;
+            }
+        }
+        URect r;
+        r.r0 = rb;
+        r.r1 = std::min(rb + rlen, sg.out_hi);
+        if (p.edge) {
+            const int64_t qf = s == 0 ? 0 : (s == strips - 1 && p.right_q0 >= 0) ? p.right_q0 : 62 * s;
+            r.q0 = qf == 0 ? 0 : qf + 1;
+            r.q1 = qf + 63 == ng - 1 ? ng : std::min(qf + 63, ng);
+        } else {
+            const int64_t per = int64_t(1) << p.lane_shift, L = 64 >> p.lane_shift;
+            r.q0 = s * per * (L - 2);
+            r.q1 = std::min(r.q0 + per * (L - 2), ng);
+        }
+        if (r.q1 <= r.q0) r.r1 = r.r0;
+        out[(size_t)(2 * unit)] = r;
+    }
+    for (int64_t i = 0; i < p.pair_units; ++i) {
+        const int64_t a = p.pairs[(size_t)(3 * i)], b = p.pairs[(size_t)(3 * i + 1)];
+        const int64_t len = std::min(a + p.pairs[(size_t)(3 * i + 2)], sg.out_hi) - a;
+        const URect ra{a, a + len, p.half_q0 + 1, p.half_hi + 1};
+        out[(size_t)(2 * (full + i))] = ra;
+        if (b >= 0) out[(size_t)(2 * (full + i) + 1)] = URect{b, b + len, ra.q0, ra.q1};
+    }
+}
+
+// Neighbour lists (CSR) of a one-segment plan of depth K: N(U) holds U and every
+// unit one of whose rectangles meets one of U's dilated by K rows and K lane-group
+// columns (the launch's K generations reach K cells, less than one group), clipped
+// to the field.  A column class (a strip, or the half strip) tiles its columns'
+// rows with disjoint row blocks: per class the blocks sorted by first row.
+void build_neighbours(gol_engine::Plan& p, int64_t ng, int K)
+{
+    std::vector<URect> rc;
+    unit_rects(p, ng, rc);
+    struct Blk {
+        int64_t r0, r1;
+        uint32_t unit;
+    };
+    const int64_t full = p.total_units - p.pair_units;
+    const size_t ncls = (size_t)p.groups + (p.pair_units ? 1 : 0);
+    std::vector<std::vector<Blk>> cls(ncls);
+    std::vector<std::pair<int64_t, int64_t>> ccol(ncls, {0, 0});
+    for (int64_t u = 0; u < p.total_units; ++u)
+        for (int k = 0; k < 2; ++k) {
+            const URect& r = rc[(size_t)(2 * u + k)];
+            if (r.r1 <= r.r0) continue;
+            const size_t c = u < full ? (size_t)(u % p.groups) : (size_t)p.groups;
+            cls[c].push_back({r.r0, r.r1, (uint32_t)u});
+            ccol[c] = {r.q0, r.q1};
+        }
+    for (auto& c : cls)
+        std::sort(c.begin(), c.end(), [](const Blk& a, const Blk& b) { return a.r0 < b.r0; });
+    p.nb_off.assign((size_t)p.total_units + 1, 0);
+    p.nb_ids.clear();
+    std::vector<uint32_t> mine;
+    for (int64_t u = 0; u < p.total_units; ++u) {
+        mine.assign(1, (uint32_t)u);
+        for (int k = 0; k < 2; ++k) {
+            const URect& r = rc[(size_t)(2 * u + k)];
+            if (r.r1 <= r.r0) continue;
+            const int64_t d0 = r.r0 - K, d1 = r.r1 + K, c0 = r.q0 - K, c1 = r.q1 + K;
+            for (size_t c = 0; c < ncls; ++c) {
+                if (cls[c].empty() || ccol[c].first >= c1 || ccol[c].second <= c0) continue;
+                auto it = std::partition_point(cls[c].begin(), cls[c].end(),
+                                               [&](const Blk& b) { return b.r1 <= d0; });
+                for (; it != cls[c].end() && it->r0 < d1; ++it) mine.push_back(it->unit);
+            }
+        }
+        std::sort(mine.begin(), mine.end());
+        mine.erase(std::unique(mine.begin(), mine.end()), mine.end());
+        p.nb_ids.insert(p.nb_ids.end(), mine.begin(), mine.end());
+        p.nb_off[(size_t)u + 1] = (uint32_t)p.nb_ids.size();
+    }
 }
 
 gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& raw)
@@ -607,6 +707,14 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
                           ? (int32_t)e->npass
                           : 1;
         }
+        // activity skip: single-GPU engines' plan of classic single-pass blocks
+        // (e->npass: a multi-pass engine rotates 4 buffers even where a plan falls
+        // back to single passes; the dev row shift moves block boundaries)
+        const bool act_plan = pi == 0 && e->nranks <= 1 && p.segs.size() == 1 && p.npass == 1 &&
+                              e->npass <= 1 && !e->xcd_shift &&
+                              !(p.hand && p.multi_blk) && p.total_units > 0 &&
+                              p.total_units < (int64_t(1) << 28);
+        if (act_plan) build_neighbours(p, (int64_t)e->ng, (int)e->K);
         max_units = std::max(max_units, p.total_units);
         any_hand |= p.hand && p.multi_blk;
         any_mp |= p.npass > 1;
@@ -628,6 +736,13 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
         HIP_TRY(hipMalloc(&p.dev, sizeof(SegDesc) * dsegs.size()));
         HIP_TRY(hipMemcpy(p.dev, dsegs.data(), sizeof(SegDesc) * dsegs.size(),
                           hipMemcpyHostToDevice));
+        if (!p.nb_off.empty()) {  // offsets, then unit ids
+            HIP_TRY(hipMalloc(&p.d_nb, sizeof(uint32_t) * (p.nb_off.size() + p.nb_ids.size())));
+            HIP_TRY(hipMemcpy(p.d_nb, p.nb_off.data(), sizeof(uint32_t) * p.nb_off.size(),
+                              hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(p.d_nb + p.nb_off.size(), p.nb_ids.data(),
+                              sizeof(uint32_t) * p.nb_ids.size(), hipMemcpyHostToDevice));
+        }
         return GOL_OK;
     };
     // Autotuner candidates (autotune_plans): for the plans of full-depth launches of
@@ -730,6 +845,13 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
             HIP_TRY(hipMalloc(&e->flags[r], par * (size_t)max_units * sizeof(uint32_t)));
             HIP_TRY(hipMemset(e->flags[r], 0, par * (size_t)max_units * sizeof(uint32_t)));
         }
+    }
+    if (e->nranks <= 1 && max_units > 0) {
+        // activity skip: the streak words of both launch parities, then the
+        // computed / skipped counters (2 per unit)
+        HIP_TRY(hipMalloc(&e->d_streak, 4 * (size_t)max_units * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(e->d_streak, 0, 4 * (size_t)max_units * sizeof(uint32_t)));
+        e->act_units = max_units;
     }
     if (any_mp && max_units > 0) {
         HIP_TRY(hipMalloc(&e->mpflags, 4 * (size_t)max_units * sizeof(uint32_t)));

@@ -67,7 +67,9 @@ def main():
         m = la.KRE.match(l)
         if not m:
             continue
-        K, rule, np_, hand, toff = (int(x) for x in m.groups())
+        K, rule, np_, hand, toff, mp = (int(x) for x in m.groups())
+        if mp:  # the multi-pass form (dev build) is not priced
+            continue
         end = next(j for j in range(i + 1, len(lines)) if not lines[j].strip())
         body = loop_body(lines[i:end])
         if body is None:
@@ -85,7 +87,7 @@ def main():
         per = {k: round(v / steps, 3) for k, v in cnt.items()}
         slots = (cnt.get("valu_full", 0) + 2 * cnt.get("valu_half", 0)) / steps
         stage_slots = (bitop3 + 2 * (dpp + align)) / steps
-        rec = {"K": K, "rule": rule, "np": np_, "hand": bool(hand), "toff": toff, "vgprs": vg.get((K, rule, np_, hand, toff)),
+        rec = {"K": K, "rule": rule, "np": np_, "hand": bool(hand), "toff": toff, "vgprs": vg.get((K, rule, np_, hand, toff, mp)),
                "loop_instrs": len(body), "stage_steps_per_iter": steps,
                "per_stage_step": per, "v_bitop3": round(bitop3 / steps, 3),
                "dpp": round(dpp / steps, 3), "v_alignbit": round(align / steps, 3),
