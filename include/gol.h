@@ -209,9 +209,14 @@ gol_status gol_reset_timing(gol_engine* e);
  * GOL_DEV_ACTIVITY_SKIP=0 in the environment at create.  gol_activity returns how
  * many units computed and how many skipped a launch, summed over the stencil
  * launches of gol_step since create or gol_reset_timing (it waits for the
- * engine's stream).  Either out pointer may be NULL.  Composite engines, group
- * members and rank engines of more than one rank keep no counters: both are 0. */
+ * engine's stream).  "Computed" = the unit stored its rows; gol_activity_copied
+ * returns how many of those did so without stage logic: a unit whose neighbourhood
+ * ended the launch before quiet copies its rows into the output buffer
+ * (copy-through, on wherever the skip is; GOL_DEV_COPY_THROUGH=0 at create turns it
+ * off and leaves the skip alone).  Any out pointer may be NULL.  Composite engines,
+ * group members and rank engines of more than one rank keep no counters: all 0. */
 gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units);
+gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units);
 
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */

@@ -37,6 +37,7 @@ EXPORTS = [
     "gol_plan_resident", "gol_plan_skew", "gol_plan_columns", "gol_plan_tuning",
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
+    "gol_activity_copied",
 ]
 
 # gol_plan_tuning's variants (plan.cpp kTuneVariantNames): 0 = the models' plan
@@ -195,6 +196,7 @@ def lib():
     L.gol_plan_model.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, i32, i32,
                                  ctypes.POINTER(PlanSummary)]
     L.gol_activity.argtypes = [vp, pu64, pu64]
+    L.gol_activity_copied.argtypes = [vp, pu64]
     L.gol_plan_neighbours.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, vp, u64,
                                       vp, u64, pu64, pu64]
     for name in ["gol_create", "gol_create_rank", "gol_load_ascii", "gol_store_ascii",
@@ -206,7 +208,7 @@ def lib():
                  "gol_create_rank_transport", "gol_round_schedule", "gol_plan_tuning",
                  "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
                  "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity",
-                 "gol_plan_neighbours"]:
+                 "gol_plan_neighbours", "gol_activity_copied"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -460,6 +462,13 @@ class Engine:
         c, k = ctypes.c_uint64(), ctypes.c_uint64()
         _check(lib().gol_activity(self._h, ctypes.byref(c), ctypes.byref(k)))
         return c.value, k.value
+
+    def activity_copied(self):
+        """Units counted as computed by activity() that stored their rows without
+        stage logic (copy-through; gol_activity_copied)."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_copied(self._h, ctypes.byref(c)))
+        return c.value
 
     def timing(self):
         t = Timing(struct_size=ctypes.sizeof(Timing))

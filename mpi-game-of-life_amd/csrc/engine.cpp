@@ -290,6 +290,14 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
         e->act_on = e->act_on && !(v && std::atoi(v) == 0) && !e->res.on && e->d_streak &&
                     !e->plans.empty() && e->plans[0].d_nb && !e->shared_device && !e->grouped &&
                     e->nbuf == 2 && e->npass <= 1 && !e->xcd_shift;
+        // copy-through of still units (GOL_DEV_COPY_THROUGH: 0 = off, 1 = in the
+        // depth-K launches only, default: in the remainder launches too) and the
+        // one-load exit of a launch after a wholly skipped one
+        // (GOL_DEV_STILL_EXIT=0 = off); neither touches the skip itself
+        const char* t = std::getenv("GOL_DEV_COPY_THROUGH");
+        e->through_on = !e->act_on ? 0 : !t ? 2 : std::max(0, std::min(2, std::atoi(t)));
+        const char* x = std::getenv("GOL_DEV_STILL_EXIT");
+        e->still_on = e->act_on && !(x && std::atoi(x) == 0);
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return GOL_OK;
@@ -617,17 +625,33 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     // counts them in act_launch; the autotuner's and every other launch: -1).  The
     // streaks live within one step: its first launch carries no history, the
     // parity alternates from there, and a launch at another depth (the remainder,
-    // always last) computes everything and leaves the streaks alone.
+    // always last) never skips and leaves the streaks alone: it reads the ones the
+    // last depth-K launch wrote, and only to copy still units through (its depths
+    // add up to less than K, so the lists, dilated by K, cover every one of them).
     if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
         a.act = e->d_streak + 2 * e->act_units;
-        if (e->act_on && !e->timing_every && depth == e->K && !hand && passes == 1 && p.d_nb &&
-            p.npass == 1 && e->nbuf == 2 && !a.xcd_shift && p.total_units <= e->act_units) {
+        a.copied = e->d_streak + 4 * e->act_units;
+        const bool may = e->act_on && !e->timing_every && !hand && passes == 1 && p.d_nb &&
+                         p.npass == 1 && e->nbuf == 2 && !a.xcd_shift &&
+                         p.total_units <= e->act_units;
+        if (may && depth == e->K) {
             const int par = e->act_launch & 1;
             a.streak_in = e->d_streak + (size_t)par * e->act_units;
             a.streak_out = e->d_streak + (size_t)(par ^ 1) * e->act_units;
             a.nb_off = p.d_nb;
             a.nb_ids = p.d_nb + p.nb_off.size();
             a.no_hist = e->act_launch == 0 ? 1 : 0;
+            a.through = e->through_on >= 1 ? 1 : 0;
+            a.busy = e->still_on ? e->d_streak + 5 * e->act_units : nullptr;
+            a.launch_idx = e->act_launch;
+            e->act_hist = par ^ 1;
+        } else if (may && depth < e->K && e->act_hist >= 0 && e->through_on >= 2) {
+            a.streak_in = e->d_streak + (size_t)e->act_hist * e->act_units;
+            a.nb_off = p.d_nb;
+            a.nb_ids = p.d_nb + p.nb_off.size();
+            a.through = 1;
+        } else {
+            e->act_hist = -1;
         }
         ++e->act_launch;
     }
@@ -1212,8 +1236,10 @@ gol_status step_single(gol_engine* e, uint64_t generations)
     // (activity skip) the launches issued or captured below are one step's: launch()
     // numbers them from 0
     e->act_launch = 0;
+    e->act_hist = -1;
     const gol_status st = step_single_launches(e, generations);
     e->act_launch = -1;
+    e->act_hist = -1;
     return st;
 }
 
@@ -1486,9 +1512,34 @@ gol_status gol_reset_timing(gol_engine* e)
     e->tm = gol_timing{};
     if (e->d_streak) {
         HIP_TRY(hipSetDevice(e->device));
+        // the computed / skipped and copied counters and the count of launches
+        // skipped as a whole
         HIP_TRY(hipMemsetAsync(e->d_streak + 2 * e->act_units, 0,
-                               2 * (size_t)e->act_units * sizeof(uint32_t), e->stream));
+                               (3 * (size_t)e->act_units + 1) * sizeof(uint32_t), e->stream));
     }
+    return GOL_OK;
+}
+
+gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    uint64_t c = 0;
+    if (!e->parts.empty()) {
+        for (auto* p : e->parts) {
+            uint64_t pc = 0;
+            gol_status st = gol_activity_copied(p, &pc);
+            if (st != GOL_OK) return st;
+            c += pc;
+        }
+    } else if (e->d_streak) {
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        std::vector<uint32_t> v((size_t)e->act_units);
+        HIP_TRY(hipMemcpy(v.data(), e->d_streak + 4 * e->act_units, v.size() * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+        for (uint32_t x : v) c += x;
+    }
+    if (copied_units) *copied_units = c;
     return GOL_OK;
 }
 
@@ -1514,6 +1565,12 @@ gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipp
             c += v[i];
             k += v[i + 1];
         }
+        // launches that every unit skipped at the one-load exit (only plan 0's
+        // launches of a step ever skip)
+        uint32_t still = 0;
+        HIP_TRY(hipMemcpy(&still, e->d_streak + 5 * e->act_units, sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+        if (!e->plans.empty()) k += (uint64_t)still * (uint64_t)e->plans[0].total_units;
     }
     if (computed_units) *computed_units = c;
     if (skipped_units) *skipped_units = k;

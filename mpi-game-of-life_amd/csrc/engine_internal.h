@@ -314,10 +314,19 @@ struct gol_engine {
     // the next stencil launch within the gol_step that is being issued, -1 outside
     // one: history never outlives a step, so nothing that touches the field
     // between steps can leave a stale streak.
+    // Then act_units "copied" counters and two words: the launches skipped as a
+    // whole and the index + 1 of the last launch in which a unit stored rows.
+    // through_on: 0 = no copy-through, 1 = launches at depth K, 2 = the remainder
+    // launches too (GOL_DEV_COPY_THROUGH, default 2); still_on: the one-load exit
+    // (GOL_DEV_STILL_EXIT=0 turns it off).  act_hist: the streak parity the step's
+    // last depth-K launch wrote, -1 while the step has no history.
     uint32_t* d_streak = nullptr;
     int64_t act_units = 0;
     bool act_on = false;
     int act_launch = -1;
+    int through_on = 0;
+    bool still_on = false;
+    int act_hist = -1;
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on

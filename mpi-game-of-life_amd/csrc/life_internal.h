@@ -118,13 +118,26 @@ struct StepArgs {
     // (plan.cpp build_neighbours; it holds the unit itself) has streak_in >= 2
     // throughout stores no row.  streak_out null = off; no_hist: the first launch
     // of a step, which ignores streak_in.  act (may be set alone): 2 counters per
-    // unit, launches computed / skipped.
+    // unit, launches computed (stored its rows) / skipped.
+    // Copy-through (`through`): a unit whose list has streak_in >= 1 throughout
+    // copies its rows from pbuf[0] to pbuf[1] without stage logic; it counts in
+    // act as computed and in copied[unit].  A launch with streak_in and no
+    // streak_out (the remainder of a step with history) reads the streaks for
+    // this only: it never skips and writes no streak.
+    // One-load exit (`busy`, 2 words): every unit that stores rows writes
+    // launch_idx + 1 (the launch's index within its step) to busy[1]; a launch
+    // that finds busy[1] < launch_idx skips as a whole, and its unit 0 counts it in
+    // busy[0].
     const uint32_t* streak_in;
     uint32_t* streak_out;
     const uint32_t* nb_off;
     const uint32_t* nb_ids;
     uint32_t* act;
+    uint32_t* copied;
+    uint32_t* busy;
     int32_t no_hist;
+    int32_t through;
+    int32_t launch_idx;
 };
 constexpr uint32_t kStreakCap = 255;
 

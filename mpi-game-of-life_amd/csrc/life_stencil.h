@@ -507,26 +507,49 @@ void life_tb_kernel(StepArgs a)
     // before this one, the rows this unit would store are the ones the output
     // buffer holds since the launch before last.  Anything else computes.
     constexpr bool kTrack = !HAND && !MP;
+    //
+    // Copy-through: when every unit of the list ended the launch before this one
+    // quiet (streak >= 1) the unit's output rows are its input rows, but the
+    // output buffer still holds the field of two launches ago: the unit copies
+    // its rows across, with no halo rows and no stage logic (`through`, below the
+    // geometry set-up).  A launch at another depth of a step with history (the
+    // remainder: streak_in without streak_out) reads the streaks for this alone;
+    // it never skips and leaves them as they are.
+    //
+    // One-load exit (StepArgs::busy): every unit that stores rows writes the
+    // launch's index + 1 to busy[1].  A word below this launch's index says that
+    // every unit skipped the launch before, so every streak is >= 3 and every
+    // unit skips this one: exit without a look at the lists or the streaks.
     uint32_t streak = 0;  // this unit's quiet launches so far (uniform)
     uint32_t acc = 0;     // OR of (generation K) ^ (generation K - 1) over the rows stored
+    bool through = false;  // (uniform) copy the unit's rows across
     if constexpr (kTrack) {
-        if (a.streak_out && !a.no_hist) {
+        if (a.streak_in && !a.no_hist) {
+            if (a.busy && a.streak_out) {
+                if (a.busy[1] < (uint32_t)a.launch_idx) {
+                    if (unit == 0 && lane == 0) a.busy[0] += 1u;
+                    return;
+                }
+            }
             const uint32_t o0 = a.nb_off[unit], o1 = a.nb_off[unit + 1];
-            bool still = o1 > o0;
+            bool still = o1 > o0, calm = o1 > o0;
             for (uint32_t j = o0; j < o1; j += 64) {
                 const uint32_t i = j + (uint32_t)lane;
                 const uint32_t s = i < o1 ? a.streak_in[a.nb_ids[i]] : 2u;
                 still = still && __builtin_amdgcn_ballot_w64(s < 2u) == 0;
+                calm = calm && __builtin_amdgcn_ballot_w64(s < 1u) == 0;
             }
             streak = __builtin_amdgcn_readfirstlane(a.streak_in[unit]);
-            if (still) {
+            if (still && a.streak_out) {
                 if (lane == 0) {
                     a.streak_out[unit] = min(streak + 1u, kStreakCap);
                     if (a.act) a.act[2 * unit + 1] += 1u;
                 }
                 return;
             }
+            through = calm && a.through;
         }
+        if (a.busy && lane == 0) a.busy[1] = (uint32_t)a.launch_idx + 1u;
     }
 #if GOL_EXP & 128
     const uint64_t wl_t0 = __builtin_amdgcn_s_memrealtime();
@@ -781,6 +804,54 @@ void life_tb_kernel(StepArgs a)
 #if GOL_EXP & 16384
     uint64_t wl_pi = 0, wl_pl = 0;
 #endif
+    if constexpr (kTrack) {
+        if (through) {
+            // Copy-through (see the prologue): exactly the rows and lanes `store`
+            // would store, rows [rb, re) in the unit's output lanes (lanes 32-63 of a
+            // pair unit: their own row block, row_off in voff), read as `ingest`
+            // reads them.  kCopyRows row loads are in flight before the first store;
+            // the last chunk loads its rows again from the block's last row on.
+            constexpr int kCopyRows = 16;
+            const char* src = reinterpret_cast<const char*>(a.pbuf[0] + (sg.base_row + rb) * a.stride) + voff;
+            char* dst = reinterpret_cast<char*>(a.pbuf[1] + (sg.base_row + rb) * a.stride) + voff;
+            const int32_t n = (int32_t)(re - rb);
+            const int32_t c_lo = (int32_t)(vlo - rb), c_hi = (int32_t)(vhi - rb);
+            auto load_rows = [&](Grp<NP> (&g)[kCopyRows], int32_t r0) {
+#pragma unroll
+                for (int j = 0; j < kCopyRows; ++j) {
+                    const int32_t r = min(r0 + j, n - 1);
+                    g[j] = *reinterpret_cast<const Grp<NP>*>(src + (int64_t)r * row_bytes);
+                }
+            };
+            auto store_rows = [&](const Grp<NP> (&g)[kCopyRows], int32_t r0) {
+#pragma unroll
+                for (int j = 0; j < kCopyRows; ++j) {
+                    const int32_t r = r0 + j;
+                    if (r < n && st_lane) {
+                        const bool ok = r >= c_lo && r < c_hi;
+                        Pl<NP> x = planes_of(g[j]);
+#pragma unroll
+                        for (int k = 0; k < NP; ++k) x.v[k] = ok ? (x.v[k] & cm.v[k]) : 0u;
+                        *reinterpret_cast<Grp<NP>*>(dst + (int64_t)r * row_bytes) = words_of(x);
+                    }
+                }
+            };
+            // (two chunks in turn, the next one's loads issued before this one's
+            // stores, measured no faster: profiles/r08/ab_copy_pipelined_rejected.jsonl)
+            for (int32_t r0 = 0; r0 < n; r0 += kCopyRows) {
+                Grp<NP> g[kCopyRows];
+                load_rows(g, r0);
+                store_rows(g, r0);
+            }
+            // quiet by the same argument, and exactly so
+            if (lane == 0) {
+                if (a.streak_out) a.streak_out[unit] = min(streak + 1u, kStreakCap);
+                if (a.act) a.act[2 * unit] += 1u;
+                if (a.copied) a.copied[unit] += 1u;
+            }
+            return;
+        }
+    }
     for (int pass = 0; pass < npass; ++pass) {
     {
         up = (pass & 1) != 0;

@@ -99,7 +99,8 @@ def main_loop_fractions(body, births):
     cands = []
     for lo, hi in loops:
         eight = [a for a, sz, _ in ins if lo <= a <= hi and sz == 8]
-        if len(eight) >= 32:
+        # (r08: the copy-through loop has 8-byte loads and stores and no stage logic)
+        if len(eight) >= 32 and any("v_alignbit" in l for a, _, l in ins if lo <= a <= hi):
             cands.append((lo, hi, eight))
     if not cands:
         return []

@@ -47,7 +47,9 @@ def loop_body(body):
             loops.append((int(m.group(1), 16) + base, a))
     cands = [(lo, hi, sum(1 for a, sz, _, _ in ins if lo <= a <= hi and sz == 8))
              for lo, hi in loops]
-    cands = [c for c in cands if c[2] >= 32]
+    # (r08: not the copy-through loop, 8-byte loads and stores without stage logic)
+    cands = [c for c in cands if c[2] >= 32 and
+             any(mn.startswith("v_alignbit") for a, _, mn, _ in ins if c[0] <= a <= c[1])]
     if not cands:
         return None
     # the steady-state loop: of the innermost candidate loops, the one with the most
