@@ -14,7 +14,8 @@
  * Conventions
  *  - Cells: bit-packed, 64 per uint64, row-major; bit j of word q is column 64q+j.
  *    Columns >= w are kept 0.  Outside the field every cell is dead
- *    (Parallel_Life_MPI.cpp:21-27).
+ *    (Parallel_Life_MPI.cpp:21-27), except on a torus (GOL_SEM_TORUS), which has no
+ *    outside.
  *  - Rule: a (birth, survive) pair of 9-bit masks, bit n <=> n live neighbours.
  *    The reference's *effective* rule is birth=0, survive=1<<2 ("B/S2"): the
  *    `count == 3` store at :44-46 is always overwritten by :47-50.
@@ -53,7 +54,23 @@ typedef enum gol_semantics {
      * into copies (:110-111, :126-127) and has no effect, so each rank's
      * extended stripe (:70-81) evolves alone and the output keeps each rank's
      * own rows (:149-175).  P = gol_config.ref_ranks. */
-    GOL_SEM_REF_STRIPES = 1
+    GOL_SEM_REF_STRIPES = 1,
+    /* One h x w field whose opposite edges are joined (periodic boundary): column
+     * w - 1 is the left neighbour of column 0 and row h - 1 the upper neighbour of
+     * row 0, for any h, w >= 1.  gol_create only, on one stream (streams 0 or 1,
+     * word_planes 0 or 2).  The engine owns an "inner" dead-border engine of the
+     * field padded with ghost cells -- G ghost rows above and below, ceil(G/64)
+     * ghost words (64 columns each) left and right: (h + 2G) x (w + 128 ceil(G/64))
+     * cells -- and gol_step runs rounds of at most G generations, each one wrap
+     * kernel, which rewrites every ghost cell from the interior, and then the inner
+     * engine's launches (gol_torus_geometry; gol_config.halo_depth sets G).  Load,
+     * store, init and digest see the h x w interior only: the same bytes, the same
+     * gol_init_random field and the same digest as a dead-border engine of h x w.
+     * Queries: gol_info reports the interior's h, w, the inner engine's tb_depth and
+     * G as halo_depth; gol_plan_*, gol_activity* and gol_*_timing report the inner
+     * engine's values (its launches cover the padded field; the wrap kernel is not
+     * timed), as a composite engine reports its first stripe. */
+    GOL_SEM_TORUS = 2
 } gol_semantics;
 
 /* Reference-effective rule and Conway's rule as (birth, survive) masks. */
@@ -74,14 +91,20 @@ typedef struct gol_config {
                               resident = 2, the resident kernel's epoch length,
                               any of 1..63 */
     uint32_t halo_depth;   /* multi-rank: halo rows exchanged per round
-                              (= generations between exchanges); 0 = auto */
+                              (= generations between exchanges); 0 = auto.
+                              GOL_SEM_TORUS: G, the generations per wrap round
+                              (= ghost rows), 1..65536; 0 = auto: the largest
+                              multiple of the inner engine's streaming depth K
+                              that is <= max(K, min(h, w) / 4) and <= 256 for
+                              fields of at most 2^25 cells, <= 128 for larger */
     uint32_t rows_per_wave;/* rows each wavefront streams per launch; 0 = auto */
     uint32_t handoff;      /* row blocks of a launch: 0 = auto (= on), 1 = off
                               (every block recomputes the K(K-1) stage-steps of
                               its vertical halo), 2 = on (each block takes the
                               rows it needs beyond its own from the block below,
                               which computed them first; tb_depth >= 4) */
-    uint32_t streams;      /* gol_create, GLOBAL only: split the field into this
+    uint32_t streams;      /* (GOL_SEM_TORUS: 0 or 1)
+                              gol_create, GLOBAL only: split the field into this
                               many row stripes advanced on their own streams of
                               the device (k-deep halos, device copies), so one
                               stripe's launch tail overlaps the others' work;
@@ -312,7 +335,9 @@ gol_status gol_rank_rows(uint64_t h, int nranks, int rank, uint64_t* row0, uint6
 gol_status gol_comm_unique_id(uint8_t id[128]);
 
 /* Engine for stripe `rank` of `nranks` of an h x w GLOBAL field; all ranks call
- * it collectively with the same id.  cfg->semantics must be GLOBAL. */
+ * it collectively with the same id.  cfg->semantics must be GLOBAL (rank engines,
+ * groups and gol_round_schedule reject GOL_SEM_TORUS: a torus is one engine on
+ * one GPU). */
 gol_status gol_create_rank(uint64_t h, uint64_t w, const gol_config* cfg, int rank,
                            int nranks, const uint8_t id[128], gol_engine** out);
 
@@ -419,6 +444,28 @@ gol_status gol_plan_neighbours(uint64_t h, uint64_t w, const gol_config* cfg, in
                                int occ_classic, int occ_hand, int64_t* rects,
                                uint32_t* offsets, uint64_t unit_cap, uint32_t* ids,
                                uint64_t id_cap, uint64_t* units, uint64_t* nids);
+
+/* ---- Torus geometry and wrap rule, host-only (no GPU needed) ---- */
+
+/* The geometry gol_create would use for an h x w engine with this config
+ * (cfg->semantics must be GOL_SEM_TORUS; the same GOL_EINVALs as gol_create):
+ * *round_gens = G generations per wrap round, *ghost_rows = G rows above and below,
+ * *ghost_words = ceil(G/64) words of 64 ghost columns left and right, and the
+ * inner engine's field *padded_h x *padded_w = (h + 2G) x (w + 128 ghost_words).
+ * Out pointers may be NULL. */
+gol_status gol_torus_geometry(uint64_t h, uint64_t w, const gol_config* cfg,
+                              uint32_t* round_gens, uint32_t* ghost_rows,
+                              uint32_t* ghost_words, uint64_t* padded_h, uint64_t* padded_w);
+
+/* The wrap on canonical packed words, through the same word gather as the wrap
+ * kernel: fills the whole padded field `out` ((h + 2 ghost_rows) rows of
+ * out_stride_words >= ceil(w/64) + 2 ghost_words words), interior included, from
+ * the h x w `field`: padded cell (y, x) = field cell ((y - ghost_rows) mod h,
+ * (x - 64 ghost_words) mod w); columns >= w + 128 ghost_words are 0.  Bits of
+ * `field` at columns >= w are ignored. */
+gol_status gol_torus_pad(const uint64_t* field, uint64_t row_stride_words, uint64_t h,
+                         uint64_t w, uint32_t ghost_rows, uint32_t ghost_words, uint64_t* out,
+                         uint64_t out_stride_words);
 
 /* ---- Multi-GPU (or multi-stripe) inside ONE process, no RCCL ----
  * `nranks` stripe engines of one GLOBAL field (the same partition and halo

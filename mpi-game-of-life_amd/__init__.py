@@ -20,7 +20,7 @@ GOL_OK, GOL_EINVAL, GOL_ENOMEM, GOL_EHIP, GOL_ERCCL, GOL_EIO, GOL_ESTATE, GOL_EX
 # gol_sched_kind (include/gol.h)
 OP_EXCHANGE, OP_WAIT_EXCHANGE, OP_LAUNCH, OP_BAND, OP_INTERIOR, OP_EXCHANGE_ASYNC = range(6)
 OP_NAMES = ["EXCHANGE", "WAIT_EXCHANGE", "LAUNCH", "BAND", "INTERIOR", "EXCHANGE_ASYNC"]
-SEM_GLOBAL, SEM_REF_STRIPES = 0, 1
+SEM_GLOBAL, SEM_REF_STRIPES, SEM_TORUS = 0, 1, 2
 
 # (birth, survive) masks; bit n <=> n live neighbours
 REF_RULE = (0, 1 << 2)  # effective rule of Parallel_Life_MPI.cpp:44-50 ("B/S2")
@@ -37,7 +37,7 @@ EXPORTS = [
     "gol_plan_resident", "gol_plan_skew", "gol_plan_columns", "gol_plan_tuning",
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
-    "gol_activity_copied",
+    "gol_activity_copied", "gol_torus_geometry", "gol_torus_pad",
 ]
 
 # gol_plan_tuning's variants (plan.cpp kTuneVariantNames): 0 = the models' plan
@@ -199,7 +199,10 @@ def lib():
     L.gol_activity_copied.argtypes = [vp, pu64]
     L.gol_plan_neighbours.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, vp, u64,
                                       vp, u64, pu64, pu64]
-    for name in ["gol_create", "gol_create_rank", "gol_load_ascii", "gol_store_ascii",
+    L.gol_torus_geometry.argtypes = [u64, u64, ctypes.POINTER(Config), ctypes.POINTER(u32),
+                                     ctypes.POINTER(u32), ctypes.POINTER(u32), pu64, pu64]
+    L.gol_torus_pad.argtypes = [vp, u64, u64, u64, u32, u32, vp, u64]
+    for name in ["gol_torus_geometry", "gol_torus_pad", "gol_create", "gol_create_rank", "gol_load_ascii", "gol_store_ascii",
                  "gol_load_packed", "gol_store_packed", "gol_init_random", "gol_step",
                  "gol_sync", "gol_digest", "gol_set_timing", "gol_get_timing",
                  "gol_reset_timing", "gol_info", "gol_rank_rows", "gol_comm_unique_id",
@@ -297,6 +300,33 @@ def plan_neighbours(h, w, cus=256, occ_classic=2, occ_hand=2, **cfg_kw):
     return rects, offs, ids[:ni.value]
 
 
+def torus_geometry(h, w, **cfg_kw):
+    """gol_torus_geometry (host only, no GPU): the geometry Engine(h, w,
+    semantics=SEM_TORUS, **cfg_kw) would use.  Returns a dict: round_gens (G,
+    generations per wrap round), ghost_rows, ghost_words, padded_h, padded_w."""
+    cfg_kw.setdefault("semantics", SEM_TORUS)
+    cfg = make_config(**cfg_kw)
+    g, gr, gw = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    ph, pw = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().gol_torus_geometry(h, w, ctypes.byref(cfg), ctypes.byref(g), ctypes.byref(gr),
+                                    ctypes.byref(gw), ctypes.byref(ph), ctypes.byref(pw)))
+    return {"round_gens": g.value, "ghost_rows": gr.value, "ghost_words": gw.value,
+            "padded_h": ph.value, "padded_w": pw.value}
+
+
+def torus_pad(arr, w, ghost_rows, ghost_words):
+    """gol_torus_pad (host only, no GPU): the packed h x w field `arr` (uint64
+    [h, >= ceil(w/64)]) wrapped into its padded field, uint64 [h + 2 ghost_rows,
+    ceil(w/64) + 2 ghost_words], by the wrap kernel's own word gather."""
+    import numpy as np
+    a = np.ascontiguousarray(arr, dtype=np.uint64)
+    h = a.shape[0]
+    out = np.zeros((h + 2 * ghost_rows, (w + 63) // 64 + 2 * ghost_words), dtype=np.uint64)
+    _check(lib().gol_torus_pad(a.ctypes.data, a.shape[1], h, w, ghost_rows, ghost_words,
+                               out.ctypes.data, out.shape[1]))
+    return out
+
+
 def unique_id() -> bytes:
     buf = ctypes.create_string_buffer(128)
     _check(lib().gol_comm_unique_id(buf))
@@ -304,7 +334,9 @@ def unique_id() -> bytes:
 
 
 class Engine:
-    """One field (or one rank's stripe of it) resident on one GPU."""
+    """One field (or one rank's stripe of it) resident on one GPU.
+    semantics=SEM_TORUS joins the field's opposite edges (one GPU, one stream;
+    halo_depth = generations per wrap round, reported back as self.halo_depth)."""
 
     def __init__(self, h, w, rule=REF_RULE, device=-1, semantics=SEM_GLOBAL, ref_ranks=1,
                  tb_depth=0, halo_depth=0, rows_per_wave=0, rank=None, nranks=1, uid=None,
@@ -507,9 +539,10 @@ class Group:
     share a GPU."""
 
     def __init__(self, h, w, nranks, devices=None, rule=REF_RULE, tb_depth=0, halo_depth=0,
-                 rows_per_wave=0, handoff=0, strip_lanes=0, word_planes=0, exchange_overlap=0):
+                 rows_per_wave=0, handoff=0, strip_lanes=0, word_planes=0, exchange_overlap=0,
+                 semantics=SEM_GLOBAL):
         self.h, self.w, self.n = h, w, nranks
-        cfg = make_config(rule, -1 if devices else 0, SEM_GLOBAL, 1, tb_depth, halo_depth,
+        cfg = make_config(rule, -1 if devices else 0, semantics, 1, tb_depth, halo_depth,
                           rows_per_wave, handoff, strip_lanes=strip_lanes,
                           word_planes=word_planes, exchange_overlap=exchange_overlap)
         hs = (ctypes.c_void_p * nranks)()

@@ -1,7 +1,7 @@
 // engine.cpp -- host side of libgol.so: the C ABI of include/gol.h.  This unit:
 // engine lifecycle, load/store, single-field and resident steps, launches and
 // timing, digests and plan queries; planning is plan.cpp, multi-GPU stripes
-// stripes.cpp (engine_internal.h).
+// stripes.cpp, torus engines torus.cpp (engine_internal.h).
 //
 // Owns device memory, the HIP streams, the halo transport (RCCL communicator,
 // a caller's host transport, or device copies inside a group) and the launch
@@ -45,7 +45,7 @@ gol_status check_cfg(const gol_config* cfg)
     if (cfg->strip_lanes != 0 && cfg->strip_lanes != 64 && cfg->strip_lanes != 32 &&
         cfg->strip_lanes != 16)
         return fail(GOL_EINVAL, "strip_lanes must be 0 (auto), 64, 32 or 16");
-    if (cfg->semantics > GOL_SEM_REF_STRIPES) return fail(GOL_EINVAL, "bad semantics");
+    if (cfg->semantics > GOL_SEM_TORUS) return fail(GOL_EINVAL, "bad semantics");
     if (cfg->resident > 2) return fail(GOL_EINVAL, "resident must be 0 (auto), 1 (off) or 2 (on)");
     if (cfg->exchange_overlap > 2)
         return fail(GOL_EINVAL, "exchange_overlap must be 0 (auto), 1 (blocking) or 2 (overlapped)");
@@ -765,6 +765,7 @@ gol_status gol_create(uint64_t h, uint64_t w, const gol_config* cfg, gol_engine*
     if (st != GOL_OK) return st;
     if (h == 0 || w == 0) return fail(GOL_EINVAL, "h and w must be >= 1");
     if (h > (1ull << 40) || w > (1ull << 40)) return fail(GOL_EINVAL, "field too large");
+    if (cfg->semantics == GOL_SEM_TORUS) return torus_create(h, w, cfg, out);
     gol_engine* e = new (std::nothrow) gol_engine();
     if (!e) return fail(GOL_ENOMEM, "host allocation");
     e->R = h;
@@ -835,6 +836,17 @@ gol_status gol_plan_model(uint64_t h, uint64_t w, const gol_config* cfg, int ran
         return fail(GOL_EINVAL, "cus and occ_classic must be >= 1, occ_hand >= 0");
     if (nranks > 1 && cfg->semantics != GOL_SEM_GLOBAL)
         return fail(GOL_EINVAL, "rank engines implement GLOBAL semantics only");
+    if (cfg->semantics == GOL_SEM_TORUS) {  // the inner engine's plan (padded field)
+        TorusGeom tg;
+        GOL_TRY(torus_geometry(h, w, cfg, &tg));
+        gol_config ic = *cfg;
+        ic.semantics = GOL_SEM_GLOBAL;
+        ic.streams = 1;
+        ic.halo_depth = 0;
+        GOL_TRY(gol_plan_model(tg.ph, tg.pw, &ic, rank, nranks, cus, occ_classic, occ_hand, out));
+        out->halo_depth = tg.G;
+        return GOL_OK;
+    }
     RankGeom g;
     gol_config c = *cfg;
     if (nranks > 1) {
@@ -902,6 +914,16 @@ gol_status gol_plan_neighbours(uint64_t h, uint64_t w, const gol_config* cfg, in
     if (h > (1ull << 40) || w > (1ull << 40)) return fail(GOL_EINVAL, "field too large");
     if (cus <= 0 || occ_classic <= 0 || occ_hand < 0)
         return fail(GOL_EINVAL, "cus and occ_classic must be >= 1, occ_hand >= 0");
+    if (cfg->semantics == GOL_SEM_TORUS) {  // the inner engine's plan (padded field)
+        TorusGeom tg;
+        GOL_TRY(torus_geometry(h, w, cfg, &tg));
+        gol_config ic = *cfg;
+        ic.semantics = GOL_SEM_GLOBAL;
+        ic.streams = 1;
+        ic.halo_depth = 0;
+        return gol_plan_neighbours(tg.ph, tg.pw, &ic, cus, occ_classic, occ_hand, rects, offsets,
+                                   unit_cap, ids, id_cap, units, nids);
+    }
     std::unique_ptr<gol_engine> e(new (std::nothrow) gol_engine());
     if (!e) return fail(GOL_ENOMEM, "host allocation");
     e->model.on = true;
@@ -938,6 +960,11 @@ extern "C" {
 void gol_destroy(gol_engine* e)
 {
     if (!e) return;
+    if (e->inner) {
+        gol_destroy(e->inner);
+        delete e;
+        return;
+    }
     if (!e->parts.empty()) {
         for (auto* p : e->parts) (void)hipStreamSynchronize(p->stream);
         for (auto* p : e->parts) gol_destroy(p);
@@ -1084,6 +1111,7 @@ extern "C" {
 gol_status gol_load_packed(gol_engine* e, const uint64_t* words, uint64_t rs)
 {
     if (!e || !words) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return torus_load_packed(e, words, rs);
     if (!e->parts.empty()) {
         for (size_t r = 0; r < e->parts.size(); ++r) {
             uint64_t r0, n;
@@ -1100,6 +1128,7 @@ gol_status gol_load_packed(gol_engine* e, const uint64_t* words, uint64_t rs)
 gol_status gol_load_ascii(gol_engine* e, const char* buf, size_t len)
 {
     if (!e || !buf) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return torus_load_ascii(e, buf, len);
     if (!e->parts.empty()) {
         if (len != e->H * (e->W + 1))
             return fail(GOL_EINVAL, "ASCII length must be rows*(w+1) = " +
@@ -1142,6 +1171,7 @@ gol_status gol_load_ascii(gol_engine* e, const char* buf, size_t len)
 gol_status gol_store_packed(gol_engine* e, uint64_t* words, uint64_t rs)
 {
     if (!e || !words) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return torus_store_packed(e, words, rs);
     if (!e->parts.empty()) {
         for (size_t r = 0; r < e->parts.size(); ++r) {
             uint64_t r0, n;
@@ -1158,6 +1188,7 @@ gol_status gol_store_packed(gol_engine* e, uint64_t* words, uint64_t rs)
 gol_status gol_store_ascii(gol_engine* e, char* buf, size_t len)
 {
     if (!e || !buf) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return torus_store_ascii(e, buf, len);
     if (!e->parts.empty()) {
         if (len != e->H * (e->W + 1))
             return fail(GOL_EINVAL, "ASCII length must be rows*(w+1) = " +
@@ -1193,6 +1224,7 @@ gol_status gol_store_ascii(gol_engine* e, char* buf, size_t len)
 gol_status gol_init_random(gol_engine* e, uint64_t seed)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return torus_init_random(e, seed);
     if (!e->parts.empty()) {
         for (auto* p : e->parts) {
             gol_status st = gol_init_random(p, seed);
@@ -1310,6 +1342,7 @@ extern "C" {
 gol_status gol_step(gol_engine* e, uint64_t generations)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return torus_step(e, generations);
     if (!e->parts.empty()) return gol_group_step(e->parts.data(), (int)e->parts.size(), generations);
     if (e->grouped) return fail(GOL_ESTATE, "group members advance with gol_group_step");
     HIP_TRY(hipSetDevice(e->device));
@@ -1321,6 +1354,7 @@ gol_status gol_step(gol_engine* e, uint64_t generations)
 gol_status gol_sync(gol_engine* e)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_sync(e->inner);
     if (!e->parts.empty()) {
         for (auto* p : e->parts) {
             gol_status st = gol_sync(p);
@@ -1338,6 +1372,7 @@ gol_status gol_sync(gol_engine* e)
 gol_status gol_digest(gol_engine* e, uint64_t* live, uint64_t* hash)
 {
     if (!e || !live || !hash) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return torus_digest_rows(e, 0, e->H, live, hash);
     if (!e->parts.empty()) {
         uint64_t L = 0, Hs = 0;
         for (auto* p : e->parts) {
@@ -1371,6 +1406,7 @@ gol_status gol_digest_rows(gol_engine* e, uint64_t row0, uint64_t rows, uint64_t
 {
     if (!e || !live || !hash) return fail(GOL_EINVAL, "null argument");
     if (row0 > e->H || rows > e->H - row0) return fail(GOL_EINVAL, "rows outside the field");
+    if (e->inner) return torus_digest_rows(e, row0, rows, live, hash);
     if (!e->parts.empty()) {
         uint64_t L = 0, Hs = 0;
         for (auto* p : e->parts) {
@@ -1409,6 +1445,7 @@ gol_status gol_digest_rows(gol_engine* e, uint64_t row0, uint64_t rows, uint64_t
 gol_status gol_plan_tuning(gol_engine* e, uint32_t* variant, float* tuned_us, float* model_us)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_plan_tuning(e->inner, variant, tuned_us, model_us);
     if (!e->parts.empty()) return gol_plan_tuning(e->parts[0], variant, tuned_us, model_us);
     if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
     const bool rk = e->nranks > 1 && e->Hx >= e->K;
@@ -1424,6 +1461,7 @@ gol_status gol_plan_tuning(gol_engine* e, uint32_t* variant, float* tuned_us, fl
 gol_status gol_plan_passes(gol_engine* e, uint32_t* passes)
 {
     if (!e || !passes) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return gol_plan_passes(e->inner, passes);
     if (!e->parts.empty()) return gol_plan_passes(e->parts[0], passes);
     if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
     const bool rk = e->nranks > 1 && e->Hx >= e->K;
@@ -1435,6 +1473,7 @@ gol_status gol_plan_passes(gol_engine* e, uint32_t* passes)
 gol_status gol_set_timing(gol_engine* e, int every)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_set_timing(e->inner, every);
     if (!e->parts.empty()) {
         for (auto* p : e->parts) {
             gol_status st = gol_set_timing(p, every);
@@ -1466,6 +1505,7 @@ static void put_timing(gol_timing* out, const gol_timing& t)
 gol_status gol_get_timing(gol_engine* e, gol_timing* out)
 {
     if (!e || !out) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return gol_get_timing(e->inner, out);
     if (!e->parts.empty()) {
         gol_timing t{};
         for (auto* p : e->parts) {
@@ -1500,6 +1540,7 @@ gol_status gol_get_timing(gol_engine* e, gol_timing* out)
 gol_status gol_reset_timing(gol_engine* e)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_reset_timing(e->inner);
     if (!e->parts.empty()) {
         for (auto* p : e->parts) {
             gol_status st = gol_reset_timing(p);
@@ -1523,6 +1564,7 @@ gol_status gol_reset_timing(gol_engine* e)
 gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_activity_copied(e->inner, copied_units);
     uint64_t c = 0;
     if (!e->parts.empty()) {
         for (auto* p : e->parts) {
@@ -1546,6 +1588,7 @@ gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units)
 gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_activity(e->inner, computed_units, skipped_units);
     uint64_t c = 0, k = 0;
     if (!e->parts.empty()) {
         for (auto* p : e->parts) {
@@ -1581,6 +1624,16 @@ gol_status gol_info(gol_engine* e, uint64_t* h, uint64_t* w, uint64_t* row0, uin
                     uint32_t* tb_depth, uint32_t* halo_depth, uint32_t* rows_per_wave)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) {  // the interior, the inner engine's depth, G
+        GOL_TRY(gol_info(e->inner, nullptr, nullptr, nullptr, nullptr, tb_depth, nullptr,
+                         rows_per_wave));
+        if (h) *h = e->H;
+        if (w) *w = e->W;
+        if (row0) *row0 = 0;
+        if (rows) *rows = e->H;
+        if (halo_depth) *halo_depth = (uint32_t)e->tG;
+        return GOL_OK;
+    }
     if (!e->parts.empty()) {
         gol_status st = gol_info(e->parts[0], nullptr, nullptr, nullptr, nullptr, tb_depth,
                                  halo_depth, rows_per_wave);
@@ -1611,6 +1664,7 @@ gol_status gol_plan_info(gol_engine* e, uint32_t* strip_lanes, uint32_t* rows_pe
                          uint32_t* word_planes)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_plan_info(e->inner, strip_lanes, rows_per_wave, word_planes);
     if (!e->parts.empty())
         return gol_plan_info(e->parts[0], strip_lanes, rows_per_wave, word_planes);
     if (word_planes) *word_planes = (uint32_t)e->planes;
@@ -1626,6 +1680,7 @@ gol_status gol_plan_skew(gol_engine* e, uint32_t* rows_old, uint32_t* rows_young
                          uint32_t* units_old)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_plan_skew(e->inner, rows_old, rows_young, units_old);
     if (!e->parts.empty()) return gol_plan_skew(e->parts[0], rows_old, rows_young, units_old);
     if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
     const auto& p = e->nranks > 1 ? e->plans[e->Hx - 1] : e->plans[0];
@@ -1639,6 +1694,7 @@ gol_status gol_plan_columns(gol_engine* e, uint32_t* strips, uint32_t* half_unit
                             uint32_t* half_groups)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_plan_columns(e->inner, strips, half_units, half_groups);
     if (!e->parts.empty()) return gol_plan_columns(e->parts[0], strips, half_units, half_groups);
     if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
     const auto& p = e->nranks > 1 ? e->plans[e->Hx - 1] : e->plans[0];
@@ -1653,6 +1709,7 @@ gol_status gol_plan_columns(gol_engine* e, uint32_t* strips, uint32_t* half_unit
 gol_status gol_plan_resident(gol_engine* e, uint32_t* on, uint32_t* bands, uint32_t* strips)
 {
     if (!e || !on) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return gol_plan_resident(e->inner, on, bands, strips);
     if (!e->parts.empty()) {
         *on = 0;
         if (bands) *bands = 0;
@@ -1669,6 +1726,7 @@ gol_status gol_plan_resident_rows(gol_engine* e, uint32_t* rows, uint32_t* band_
                                   uint32_t* epoch, uint32_t* swap_every)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_plan_resident_rows(e->inner, rows, band_rows, epoch, swap_every);
     const bool on = e->parts.empty() && e->res.on;
     if (rows) *rows = on ? (uint32_t)e->res.rows : 0u;
     if (band_rows) *band_rows = on ? (uint32_t)e->res.band_rows : 0u;
@@ -1680,6 +1738,7 @@ gol_status gol_plan_resident_rows(gol_engine* e, uint32_t* rows, uint32_t* band_
 gol_status gol_plan_handoff(gol_engine* e, uint32_t* handoff)
 {
     if (!e || !handoff) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return gol_plan_handoff(e->inner, handoff);
     if (!e->parts.empty()) return gol_plan_handoff(e->parts[0], handoff);
     if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
     const auto& p = e->nranks > 1 ? e->plans[e->Hx - 1] : e->plans[0];

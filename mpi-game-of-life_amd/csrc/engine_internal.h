@@ -8,6 +8,8 @@
 //   stripes.cpp  multi-GPU stripes: rank geometry and halo rounds, the exchange
 //                (RCCL, host transport, device copies) and its mode, rank and
 //                group engines
+//   torus.cpp    torus engines: ghost-zone geometry, wrap rounds around an inner
+//                dead-border engine, I/O and digests of the interior
 // Mirrors main()'s flow in Parallel_Life_MPI.cpp:190-240: create
 // (readGridFromFile's allocation :88-89) -> load (:91-99) -> step (the epoch loop
 // :215-221 with the halo exchange :104-145) -> store (:157-164).
@@ -241,6 +243,13 @@ struct gol_engine {
     // launch tail overlaps the others' work; every call is routed to the parts
     std::vector<gol_engine*> parts;
 
+    // torus engine (gol_create, GOL_SEM_TORUS; torus.cpp): the h x w interior lives
+    // inside `inner`, a single-stream GLOBAL engine of the padded field, at row tG,
+    // word tGx; gol_step wraps the ghosts every tG generations.  H, W, wq, lastmask
+    // describe the interior; every call is routed to torus.cpp or to `inner`
+    gol_engine* inner = nullptr;
+    uint64_t tG = 0, tGx = 0;
+
     uint64_t buf_rows = 0;
     // state buffers: 2, or 4 with multi-pass launches (a launch of P <= 3 passes
     // reads buf[cur] and writes buf[cur + 1 .. cur + P], mod nbuf); those also hold
@@ -416,6 +425,24 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
 void decide_passes(gol_engine* e, size_t words);
 gol_status autotune_plans(gol_engine* e);
 void resolve_aliases(gol_engine* e);
+
+// ---- torus.cpp
+// Geometry of a torus engine: inner depth K (streaming launches), generations per
+// wrap round = ghost rows G, ghost words Gx per side, padded field ph x pw.
+struct TorusGeom {
+    uint32_t K = 0, G = 0;
+    uint64_t Gx = 0, ph = 0, pw = 0;
+};
+gol_status torus_geometry(uint64_t h, uint64_t w, const gol_config* cfg, TorusGeom* g);
+gol_status torus_create(uint64_t h, uint64_t w, const gol_config* cfg, gol_engine** out);
+gol_status torus_step(gol_engine* e, uint64_t generations);
+gol_status torus_load_packed(gol_engine* e, const uint64_t* words, uint64_t rs);
+gol_status torus_store_packed(gol_engine* e, uint64_t* words, uint64_t rs);
+gol_status torus_load_ascii(gol_engine* e, const char* buf, size_t len);
+gol_status torus_store_ascii(gol_engine* e, char* buf, size_t len);
+gol_status torus_init_random(gol_engine* e, uint64_t seed);
+gol_status torus_digest_rows(gol_engine* e, uint64_t row0, uint64_t rows, uint64_t* live,
+                             uint64_t* hash);
 
 // ---- stripes.cpp
 uint32_t pick_depth(uint32_t K, uint64_t remaining);

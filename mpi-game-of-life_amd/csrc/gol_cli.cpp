@@ -15,6 +15,10 @@
 // --gpus G splits that domain into G row stripes on devices 0..G-1 of this
 // process with k-deep halo rounds over xGMI peer copies (gol_create_group);
 // --stripes S runs S stripes round-robin on the G devices (S >= G).
+// --torus joins the field's opposite edges (GOL_SEM_TORUS): same files, same
+// output.txt format; one engine on one GPU, so not with --ref-ranks, nor with
+// --gpus or --stripes above 1.  --halo-depth then sets the generations per wrap
+// round.
 //
 // Deviation: where the reference prints an error and continues with
 // uninitialised values (:206) or an unopened file (:186), this program exits
@@ -71,8 +75,10 @@ void usage()
 {
     std::cerr << "usage: gol [--dir DIR] [--ref-ranks P] [--rule ref|conway|B3/S23]\n"
                  "           [--tb-depth K] [--rows-per-wave N] [--device D]\n"
-                 "           [--gpus G] [--stripes S] [--halo-depth H]\n"
-                 "Reads grid_size_data.txt and data.txt, writes output.txt.\n";
+                 "           [--gpus G] [--stripes S] [--halo-depth H] [--torus]\n"
+                 "Reads grid_size_data.txt and data.txt, writes output.txt.\n"
+                 "--torus: the field's opposite edges are joined (periodic boundary);\n"
+                 "         not with --ref-ranks, nor with --gpus / --stripes above 1.\n";
 }
 
 bool read_file(const std::string& path, size_t need, std::vector<char>& out)
@@ -97,6 +103,7 @@ int main(int argc, char** argv)
     const auto t0 = std::chrono::steady_clock::now();  // MPI_Wtime() at :199
     std::string dir = ".";
     int gpus = 0, stripes = 0;
+    bool torus = false, ref_ranks = false;
     gol_config cfg;
     gol_config_init(&cfg);
     for (int i = 1; i < argc; ++i) {
@@ -112,7 +119,9 @@ int main(int argc, char** argv)
         else if (a == "--ref-ranks") {
             cfg.ref_ranks = (uint32_t)std::strtoul(next().c_str(), nullptr, 10);
             cfg.semantics = GOL_SEM_REF_STRIPES;
-        } else if (a == "--rule") {
+            ref_ranks = true;
+        } else if (a == "--torus") torus = true;
+        else if (a == "--rule") {
             if (!parse_rule(next(), &cfg.birth_mask, &cfg.survive_mask)) {
                 std::cerr << "bad rule\n";
                 return 2;
@@ -130,6 +139,16 @@ int main(int argc, char** argv)
             usage();
             return 2;
         }
+    }
+
+    if (torus) {
+        if (ref_ranks || gpus > 1 || stripes > 1) {
+            std::cerr << "--torus is one field on one GPU; drop --ref-ranks, --gpus and --stripes"
+                      << std::endl;
+            return 2;
+        }
+        cfg.semantics = GOL_SEM_TORUS;
+        gpus = stripes = 0;  // (--gpus 1 / --stripes 1: the one engine below)
     }
 
     long long h = 0, w = 0, epochs = 0;

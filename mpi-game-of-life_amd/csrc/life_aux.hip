@@ -6,6 +6,7 @@
 
 #include "bitlayout.h"
 #include "life_internal.h"
+#include "torus_wrap.h"
 
 namespace gol {
 
@@ -96,10 +97,11 @@ template <int NP>
 __global__ __launch_bounds__(256) void init_random_kernel(uint64_t* buf, int64_t stride,
                                                           int64_t wq, uint64_t lastmask,
                                                           int64_t row_base, int64_t glob_row0,
-                                                          int64_t nrows, uint64_t seed)
+                                                          int64_t nrows, uint64_t seed,
+                                                          int64_t row_words)
 {
     constexpr int G = NP / 2;
-    const int64_t gpr = stride / G;  // lane groups per buffer row
+    const int64_t gpr = row_words / G;  // lane groups written per buffer row
     const int64_t total = nrows * gpr;
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total;
          k += (int64_t)gridDim.x * blockDim.x) {
@@ -123,7 +125,7 @@ template <int NP>
 __global__ __launch_bounds__(256) void digest_kernel(const uint64_t* buf, int64_t stride,
                                                      int64_t wq, int64_t ng, int64_t row_base,
                                                      int64_t glob_row0, int64_t nrows,
-                                                     unsigned long long* acc)
+                                                     unsigned long long* acc, uint64_t lastmask)
 {
     constexpr int G = NP / 2;
     const int64_t total = nrows * ng;
@@ -139,6 +141,8 @@ __global__ __launch_bounds__(256) void digest_kernel(const uint64_t* buf, int64_
         for (int j = 0; j < G; ++j) {
             const int64_t idx = gq * G + j;
             if (idx < wq) {
+                // (a torus interior's last word also holds ghost columns)
+                if (idx == wq - 1) c[j] &= lastmask;
                 live += (uint64_t)__popcll(c[j]);
                 const uint64_t h = (uint64_t)(glob_row0 + i) * (uint64_t)wq + (uint64_t)idx;
                 hash += splitmix64_at(c[j] ^ splitmix64_at(0, h), 0);
@@ -215,6 +219,46 @@ __global__ __launch_bounds__(256) void ascii_unpack_kernel(const uint64_t* src, 
     }
 }
 
+// Torus wrap: one thread per ghost or straddling word of the padded field (2-plane
+// stored words).  The 2G ghost rows take all wq_pad words; an interior row takes
+// its Gx left ghost words and the words from the one that holds column w on
+// (`side` words: the straddling word, if w % 64 != 0, and the right ghosts).
+// Sources are interior words only; the one word that is both source and target,
+// the straddling word, keeps its interior bits (imask), and the gather never looks
+// at a source bit at or beyond column w (torus_wrap.h), so the order in which the
+// threads run does not matter.
+__global__ __launch_bounds__(256) void torus_wrap_kernel(uint64_t* buf, int64_t stride, int64_t h,
+                                                         int64_t w, int64_t G, int64_t Gx,
+                                                         int64_t wq_pad)
+{
+    const int64_t full = w >> 6;             // interior words without ghost columns
+    const int64_t side = wq_pad - full;      // words per interior row: Gx + (rest)
+    const int64_t ghost_words = 2 * G * wq_pad;
+    const int64_t total = ghost_words + h * side;
+    const int64_t x_end = w + 64 * Gx;
+    const uint64_t imask = (w & 63) ? ((1ull << (w & 63)) - 1ull) : 0ull;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        int64_t row, q;  // padded row and word
+        if (k < ghost_words) {
+            const int64_t i = k / wq_pad;
+            q = k - i * wq_pad;
+            row = i < G ? i : h + i;  // rows [0, G) and [h + G, h + 2G)
+        } else {
+            const int64_t j = k - ghost_words, i = j / side, c = j - i * side;
+            row = G + i;
+            q = c < Gx ? c : full + c;  // [0, Gx) and [Gx + full, wq_pad)
+        }
+        const uint64_t* src = buf + (G + gol_torus_mod(row - G, h)) * stride + Gx;
+        uint64_t v = gol_torus_gather([src](int64_t i) { return gol_join64(src[i]); }, w, q - Gx,
+                                      x_end);
+        uint64_t* dst = buf + row * stride + q;
+        if (row >= G && row < G + h && q == Gx + full && imask)
+            v = (gol_join64(*dst) & imask) | (v & ~imask);
+        *dst = gol_split64(v);
+    }
+}
+
 dim3 grid_for(int64_t items, int64_t per_block, int64_t cap)
 {
     int64_t blocks = (items + per_block - 1) / per_block;
@@ -226,16 +270,17 @@ dim3 grid_for(int64_t items, int64_t per_block, int64_t cap)
 
 hipError_t launch_init_random(uint64_t* buf, int64_t stride, int64_t wq, uint64_t lastmask,
                               int64_t row_base, int64_t glob_row0, int64_t nrows, uint64_t seed,
-                              int planes, hipStream_t s)
+                              int planes, hipStream_t s, int64_t row_words)
 {
     if (nrows <= 0) return hipSuccess;
-    const dim3 grid = grid_for(nrows * stride / (planes / 2), 256, 8192);
+    if (row_words <= 0) row_words = stride;
+    const dim3 grid = grid_for(nrows * row_words / (planes / 2), 256, 8192);
     if (planes == 4)
         hipLaunchKernelGGL(init_random_kernel<4>, grid, dim3(256), 0, s, buf, stride, wq, lastmask,
-                           row_base, glob_row0, nrows, seed);
+                           row_base, glob_row0, nrows, seed, row_words);
     else
         hipLaunchKernelGGL(init_random_kernel<2>, grid, dim3(256), 0, s, buf, stride, wq, lastmask,
-                           row_base, glob_row0, nrows, seed);
+                           row_base, glob_row0, nrows, seed, row_words);
     return hipGetLastError();
 }
 
@@ -269,16 +314,28 @@ hipError_t launch_ascii_unpack(const uint64_t* src, int64_t stride, int64_t rows
 
 hipError_t launch_digest(const uint64_t* buf, int64_t stride, int64_t wq, int64_t ng,
                          int64_t row_base, int64_t glob_row0, int64_t nrows,
-                         unsigned long long* acc, int planes, hipStream_t s)
+                         unsigned long long* acc, int planes, hipStream_t s, uint64_t lastmask)
 {
     if (nrows <= 0) return hipSuccess;
     const dim3 grid = grid_for(nrows * ng, 256, 8192);
     if (planes == 4)
         hipLaunchKernelGGL(digest_kernel<4>, grid, dim3(256), 0, s, buf, stride, wq, ng, row_base,
-                           glob_row0, nrows, acc);
+                           glob_row0, nrows, acc, lastmask);
     else
         hipLaunchKernelGGL(digest_kernel<2>, grid, dim3(256), 0, s, buf, stride, wq, ng, row_base,
-                           glob_row0, nrows, acc);
+                           glob_row0, nrows, acc, lastmask);
+    return hipGetLastError();
+}
+
+hipError_t launch_torus_wrap(uint64_t* buf, int64_t stride, int64_t h, int64_t w, int64_t G,
+                             int64_t Gx, hipStream_t s)
+{
+    if (h <= 0 || w <= 0 || G <= 0 || Gx <= 0) return hipErrorInvalidValue;
+    const int64_t wq_pad = (w + 128 * Gx + 63) / 64;
+    if (stride < wq_pad) return hipErrorInvalidValue;
+    const int64_t total = 2 * G * wq_pad + h * (wq_pad - (w >> 6));
+    hipLaunchKernelGGL(torus_wrap_kernel, grid_for(total, 256, 8192), dim3(256), 0, s, buf, stride,
+                       h, w, G, Gx, wq_pad);
     return hipGetLastError();
 }
 

@@ -261,10 +261,12 @@ hipError_t launch_resident_mb(const ResArgs& a, int rows, int mb, RuleKind rule,
 int resident_mb_blocks_per_cu(int rows, int mb, RuleKind rule);
 
 // Device-side synthetic init: buffer rows [row_base, row_base+nrows) get field
-// rows [glob_row0, glob_row0+nrows).
+// rows [glob_row0, glob_row0+nrows).  row_words: the words written per row (the
+// field's, then zeros), 0 = the whole stride; a torus interior (torus.cpp), whose
+// rows sit inside longer buffer rows, passes its own width.
 hipError_t launch_init_random(uint64_t* buf, int64_t stride, int64_t wq, uint64_t lastmask,
                               int64_t row_base, int64_t glob_row0, int64_t nrows,
-                              uint64_t seed, int planes, hipStream_t s);
+                              uint64_t seed, int planes, hipStream_t s, int64_t row_words = 0);
 
 // ASCII codec: `rows` lines of w cell bytes + '\n' (device memory) <-> stored
 // lane groups (ng per row) at dst/src with `stride` words per row.  *bad is set
@@ -275,9 +277,19 @@ hipError_t launch_ascii_unpack(const uint64_t* src, int64_t stride, int64_t rows
                                int64_t ng, char* dst, int planes, hipStream_t s);
 
 // Adds popcount and hash of buffer rows [row_base, row_base+nrows) (field rows
-// glob_row0..) into acc[0], acc[1].
+// glob_row0..) into acc[0], acc[1].  lastmask: the field's bits of word wq - 1
+// (all ones where the buffer keeps columns >= w at 0; a torus interior has ghost
+// cells there).
 hipError_t launch_digest(const uint64_t* buf, int64_t stride, int64_t wq, int64_t ng,
                          int64_t row_base, int64_t glob_row0, int64_t nrows,
-                         unsigned long long* acc, int planes, hipStream_t s);
+                         unsigned long long* acc, int planes, hipStream_t s,
+                         uint64_t lastmask = ~0ull);
+
+// Torus wrap (GOL_SEM_TORUS, torus.cpp): rewrites every ghost cell of a padded
+// 2-plane field from its h x w interior by the rule of torus_wrap.h.  `buf` is the
+// padded field's row 0, `stride` its words per row; the interior starts at row G,
+// word Gx; wq_pad = ceil((w + 128 Gx) / 64) words per row are the field's.
+hipError_t launch_torus_wrap(uint64_t* buf, int64_t stride, int64_t h, int64_t w, int64_t G,
+                             int64_t Gx, hipStream_t s);
 
 }  // namespace gol
