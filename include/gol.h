@@ -323,6 +323,57 @@ gol_status gol_plan_passes(gol_engine* e, uint32_t* passes);
 gol_status gol_digest_rows(gol_engine* e, uint64_t row0, uint64_t rows, uint64_t* live,
                            uint64_t* hash);
 
+/* ---- Region I/O: rectangles of a field that stays on the GPU ----
+ * A window is canonical and packed like gol_load_packed's words: bit j of word q of
+ * window row i is field cell (y + i, x + 64q + j); row_stride_words >= ceil(rw/64).
+ * Only the window moves between host and device, never the field, and every call
+ * returns after the host buffer has been filled or consumed.
+ * Bounds (else GOL_EINVAL): y + rh <= h and x + rw <= w.  On a torus
+ * (GOL_SEM_TORUS) y < h, x < w, rh <= h, rw <= w, and the rectangle may cross either
+ * seam or both: window cell (i, j) is field cell ((y + i) mod h, (x + j) mod w).
+ * rh == 0 or rw == 0: GOL_OK, nothing done.
+ * Rank engines and group members take the coordinates of the global field and
+ * apply the part of the rectangle that lies in their own rows. */
+
+/* Reads the rectangle; bits at or beyond rw in a row's last word are written 0.
+ * Waits for the engine's work first, like gol_store_packed.  A rank engine
+ * zero-fills the window rows it does not own (OR the ranks' windows together). */
+gol_status gol_read_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                         uint64_t* words, uint64_t row_stride_words);
+
+/* Combines the window into the field between steps: SET copies it, OR / XOR
+ * combine, CLEAR is field AND NOT window; an unknown op is GOL_EINVAL.  Window bits
+ * at or beyond rw are ignored, and no cell outside the rectangle changes.  Like a
+ * load it finishes the engine's streams first, and the next gol_step of a stripe
+ * engine starts with a halo exchange; so for rank engines it is collective like a
+ * load: every rank calls it with the same rectangle before the next gol_step.
+ * GOL_SEM_REF_STRIPES engines return GOL_ESTATE (their overlap rows exist twice
+ * and evolve apart: "the cell" is ambiguous); reads and densities work there. */
+typedef enum gol_rect_op {
+    GOL_RECT_SET = 0,
+    GOL_RECT_OR = 1,
+    GOL_RECT_XOR = 2,
+    GOL_RECT_CLEAR = 3
+} gol_rect_op;
+gol_status gol_write_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                          const uint64_t* words, uint64_t row_stride_words, uint32_t op);
+
+/* Live cells per block: the window is tiled with by x bx blocks from its corner
+ * (edge blocks partial), counts[bi * row_stride + bj] = live cells of block (bi,
+ * bj), row_stride >= ceil(rw/bx).  GOL_EINVAL if by, bx, rh or rw is 0 or by * bx
+ * > UINT32_MAX.  Only the counts move to the host.  A rank engine counts its own
+ * rows only (add the ranks' counts, as with gol_digest). */
+gol_status gol_density(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                       uint64_t by, uint64_t bx, uint32_t* counts, uint64_t row_stride);
+
+/* Host-only, no GPU: the blit the kernels run, on canonical packed words.  Bits
+ * [sx, sx + cols) of each of `rows` rows of src are combined with op (gol_rect_op)
+ * onto bits [dx, dx + cols) of dst; no other bit of dst changes.  Strides in words,
+ * src_stride_words >= ceil((sx + cols)/64), dst_stride_words >= ceil((dx + cols)/64). */
+gol_status gol_rect_blit(const uint64_t* src, uint64_t src_stride_words, uint64_t sx,
+                         uint64_t* dst, uint64_t dst_stride_words, uint64_t dx, uint64_t rows,
+                         uint64_t cols, uint32_t op);
+
 /* ---- Multi-GPU, one process per GPU (replaces the MPI stripes :70-81 and the
  * halo exchange :104-145 with RCCL send/recv over xGMI) ---- */
 

@@ -21,6 +21,8 @@ GOL_OK, GOL_EINVAL, GOL_ENOMEM, GOL_EHIP, GOL_ERCCL, GOL_EIO, GOL_ESTATE, GOL_EX
 OP_EXCHANGE, OP_WAIT_EXCHANGE, OP_LAUNCH, OP_BAND, OP_INTERIOR, OP_EXCHANGE_ASYNC = range(6)
 OP_NAMES = ["EXCHANGE", "WAIT_EXCHANGE", "LAUNCH", "BAND", "INTERIOR", "EXCHANGE_ASYNC"]
 SEM_GLOBAL, SEM_REF_STRIPES, SEM_TORUS = 0, 1, 2
+# gol_rect_op: how write_rect / rect_blit combine the window with the field
+RECT_SET, RECT_OR, RECT_XOR, RECT_CLEAR = range(4)
 
 # (birth, survive) masks; bit n <=> n live neighbours
 REF_RULE = (0, 1 << 2)  # effective rule of Parallel_Life_MPI.cpp:44-50 ("B/S2")
@@ -38,6 +40,7 @@ EXPORTS = [
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
     "gol_activity_copied", "gol_torus_geometry", "gol_torus_pad",
+    "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
 ]
 
 # gol_plan_tuning's variants (plan.cpp kTuneVariantNames): 0 = the models' plan
@@ -202,6 +205,12 @@ def lib():
     L.gol_torus_geometry.argtypes = [u64, u64, ctypes.POINTER(Config), ctypes.POINTER(u32),
                                      ctypes.POINTER(u32), ctypes.POINTER(u32), pu64, pu64]
     L.gol_torus_pad.argtypes = [vp, u64, u64, u64, u32, u32, vp, u64]
+    L.gol_read_rect.argtypes = [vp, u64, u64, u64, u64, vp, u64]
+    L.gol_write_rect.argtypes = [vp, u64, u64, u64, u64, vp, u64, u32]
+    L.gol_density.argtypes = [vp, u64, u64, u64, u64, u64, u64, vp, u64]
+    L.gol_rect_blit.argtypes = [vp, u64, u64, vp, u64, u64, u64, u64, u32]
+    for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit"]:
+        getattr(L, name).restype = ctypes.c_int
     for name in ["gol_torus_geometry", "gol_torus_pad", "gol_create", "gol_create_rank", "gol_load_ascii", "gol_store_ascii",
                  "gol_load_packed", "gol_store_packed", "gol_init_random", "gol_step",
                  "gol_sync", "gol_digest", "gol_set_timing", "gol_get_timing",
@@ -325,6 +334,23 @@ def torus_pad(arr, w, ghost_rows, ghost_words):
     _check(lib().gol_torus_pad(a.ctypes.data, a.shape[1], h, w, ghost_rows, ghost_words,
                                out.ctypes.data, out.shape[1]))
     return out
+
+
+def rect_blit(src, sx, dst, dx, rows, cols, op=RECT_SET):
+    """gol_rect_blit (host only, no GPU): combines bits [sx, sx + cols) of the first
+    `rows` rows of the packed uint64 array `src` onto bits [dx, dx + cols) of `dst`
+    (a C-contiguous uint64 array, changed in place) with `op`, through the word
+    gather and merge the rectangle kernels use."""
+    import numpy as np
+    a = np.ascontiguousarray(src, dtype=np.uint64)
+    if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint64 and dst.ndim == 2
+            and dst.flags.c_contiguous and dst.flags.writeable):
+        raise GolError(GOL_EINVAL, "dst must be a writeable C-contiguous 2-D uint64 array")
+    if a.ndim != 2 or rows > a.shape[0] or rows > dst.shape[0]:
+        raise GolError(GOL_EINVAL, "src and dst must be 2-D with at least `rows` rows")
+    _check(lib().gol_rect_blit(a.ctypes.data, a.shape[1], sx, dst.ctypes.data, dst.shape[1], dx,
+                               rows, cols, op))
+    return dst
 
 
 def unique_id() -> bytes:
@@ -455,6 +481,33 @@ class Engine:
 
     def init_random(self, seed=1):
         _check(lib().gol_init_random(self._h, seed))
+
+    def read_rect(self, y, x, rh, rw):
+        """The rh x rw window at field cell (y, x) as packed uint64 [rh, ceil(rw/64)]
+        (gol_read_rect: only the window leaves the GPU).  A torus window may cross
+        the seams; a rank engine or group member fills its own rows, 0 elsewhere."""
+        import numpy as np
+        a = np.zeros((rh, (rw + 63) // 64), dtype=np.uint64)
+        _check(lib().gol_read_rect(self._h, y, x, rh, rw, a.ctypes.data, a.shape[1]))
+        return a
+
+    def write_rect(self, y, x, arr, rw, op=RECT_SET):
+        """Combines the packed window `arr` (uint64 [rh, >= ceil(rw/64)], rw columns)
+        into the field at cell (y, x) with `op` (RECT_SET / OR / XOR / CLEAR), between
+        steps (gol_write_rect).  Rank engines: every rank calls it, like a load."""
+        import numpy as np
+        a = np.ascontiguousarray(arr, dtype=np.uint64)
+        if a.ndim != 2:
+            raise GolError(GOL_EINVAL, "the window must be a 2-D uint64 array")
+        _check(lib().gol_write_rect(self._h, y, x, a.shape[0], rw, a.ctypes.data, a.shape[1], op))
+
+    def density(self, y, x, rh, rw, by, bx):
+        """Live cells per by x bx block of the rh x rw window at (y, x): uint32
+        [ceil(rh/by), ceil(rw/bx)] (gol_density; a rank engine counts its own rows)."""
+        import numpy as np
+        c = np.zeros((-(-rh // by) if by else 0, -(-rw // bx) if bx else 0), dtype=np.uint32)
+        _check(lib().gol_density(self._h, y, x, rh, rw, by, bx, c.ctypes.data, c.shape[1]))
+        return c
 
     def step(self, gens):
         _check(lib().gol_step(self._h, gens))
@@ -587,6 +640,25 @@ class Group:
 
     def store_ascii(self) -> bytes:
         return b"".join(m.store_ascii() for m in self.members)
+
+    def read_rect(self, y, x, rh, rw):
+        """Engine.read_rect of the whole field: the members' windows OR-ed."""
+        out = self.members[0].read_rect(y, x, rh, rw)
+        for m in self.members[1:]:
+            out |= m.read_rect(y, x, rh, rw)
+        return out
+
+    def write_rect(self, y, x, arr, rw, op=RECT_SET):
+        """Engine.write_rect on every member (each applies its own rows)."""
+        for m in self.members:
+            m.write_rect(y, x, arr, rw, op)
+
+    def density(self, y, x, rh, rw, by, bx):
+        """Engine.density of the whole field: the members' counts added."""
+        out = self.members[0].density(y, x, rh, rw, by, bx)
+        for m in self.members[1:]:
+            out += m.density(y, x, rh, rw, by, bx)
+        return out
 
     def digest(self):
         live = hsh = 0

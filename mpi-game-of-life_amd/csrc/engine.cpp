@@ -1011,6 +1011,7 @@ void gol_destroy(gol_engine* e)
     for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second.exec);
     if (e->d_acc) (void)hipFree(e->d_acc);
     if (e->d_flag) (void)hipFree(e->d_flag);
+    if (e->rect_stage) (void)hipFree(e->rect_stage);
     for (const auto* pend : {&e->ev_pending, &e->ev_xpending})
         for (auto& p : *pend) {
             (void)hipEventDestroy(p.first);
@@ -1439,6 +1440,259 @@ gol_status gol_digest_rows(gol_engine* e, uint64_t row0, uint64_t rows, uint64_t
     *live = acc[0];
     *hash = acc[1];
     return check_err(e);
+}
+
+}  // extern "C"
+
+// ---- Region I/O: gol_read_rect / gol_write_rect / gol_density.  A call
+// becomes non-wrapping pieces in the coordinates of a leaf engine (one with
+// buffers); a piece is cut along the leaf's regions, whose rows are contiguous in
+// the buffer, and each cut runs one kernel on a staging buffer of the cut's size.
+namespace golh __attribute__((visibility("hidden"))) {
+
+// Device staging of one cut.  Up to kRectStageKeep bytes it is the engine's own
+// buffer, kept and grown between calls (every use ends with the stream idle), so a
+// small read, write or density pays no allocation; a larger one is transient.
+constexpr size_t kRectStageKeep = 64u << 20;
+struct RectStage {
+    char* p = nullptr;
+    bool own = false;
+    ~RectStage()
+    {
+        if (own && p) (void)hipFree(p);
+    }
+};
+
+static gol_status rect_stage(gol_engine* e, size_t bytes, RectStage* s)
+{
+    if (bytes > kRectStageKeep) {
+        HIP_TRY(hipMalloc(&s->p, bytes));
+        s->own = true;
+        return GOL_OK;
+    }
+    if (e->rect_stage_bytes < bytes) {
+        if (e->rect_stage) HIP_TRY(hipFree(e->rect_stage));
+        e->rect_stage = nullptr;
+        e->rect_stage_bytes = 0;
+        HIP_TRY(hipMalloc(&e->rect_stage, bytes));
+        e->rect_stage_bytes = bytes;
+    }
+    s->p = e->rect_stage;
+    return GOL_OK;
+}
+
+// rows of region r inside the piece: field rows [*lo, *hi)
+static bool piece_rows(const Region& r, const RectPiece& p, uint64_t* lo, uint64_t* hi)
+{
+    *lo = std::max<uint64_t>(r.glob_row, p.frow);
+    *hi = std::min<uint64_t>(r.glob_row + r.rows, p.frow + p.rows);
+    return *hi > *lo;
+}
+
+gol_status leaf_read(gol_engine* e, const std::vector<Region>& regs, uint64_t word_off,
+                     const RectPiece* pcs, size_t npc, uint64_t* words, uint64_t rs)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    GOL_TRY(join_side_streams(e));
+    std::vector<uint64_t> tmp;
+    for (size_t k = 0; k < npc; ++k) {
+        const RectPiece& p = pcs[k];
+        const uint64_t pw = (p.cols + 63) / 64;
+        for (const auto& r : regs) {
+            uint64_t lo, hi;
+            if (!piece_rows(r, p, &lo, &hi) || !p.cols) continue;
+            const uint64_t n = hi - lo;
+            RectStage d;
+            GOL_TRY(rect_stage(e, (size_t)n * pw * 8, &d));
+            HIP_TRY(gol::launch_rect_read(e->buf[e->cur] + word_off, (int64_t)e->stride,
+                                          (int64_t)(r.buf_row + (lo - r.glob_row)),
+                                          (int64_t)p.fcol, (int64_t)n, (int64_t)p.cols,
+                                          (uint64_t*)d.p, (int64_t)pw, e->planes, e->stream));
+            tmp.resize((size_t)n * pw);
+            HIP_TRY(hipMemcpyAsync(tmp.data(), d.p, tmp.size() * 8, hipMemcpyDeviceToHost,
+                                   e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            for (uint64_t i = 0; i < n; ++i)
+                gol_rect_blit_row(tmp.data() + i * pw, 0, words + (p.wrow + lo - p.frow + i) * rs,
+                                  (int64_t)p.wcol, (int64_t)p.cols, GOL_RECT_SET);
+        }
+    }
+    return check_err(e);
+}
+
+gol_status leaf_write(gol_engine* e, const std::vector<Region>& regs, uint64_t word_off,
+                      const RectPiece* pcs, size_t npc, const uint64_t* words, uint64_t rs,
+                      uint32_t op)
+{
+    // as a load: every stream of the engine finished, and the next step of a stripe
+    // engine exchanges halos first (whether or not the rectangle meets its rows)
+    GOL_TRY(quiesce(e));
+    std::vector<uint64_t> tmp;
+    for (size_t k = 0; k < npc; ++k) {
+        const RectPiece& p = pcs[k];
+        const uint64_t pw = (p.cols + 63) / 64;
+        for (const auto& r : regs) {
+            uint64_t lo, hi;
+            if (!piece_rows(r, p, &lo, &hi) || !p.cols) continue;
+            const uint64_t n = hi - lo;
+            tmp.assign((size_t)n * pw, 0);
+            for (uint64_t i = 0; i < n; ++i)
+                gol_rect_blit_row(words + (p.wrow + lo - p.frow + i) * rs, (int64_t)p.wcol,
+                                  tmp.data() + i * pw, 0, (int64_t)p.cols, GOL_RECT_SET);
+            RectStage d;
+            GOL_TRY(rect_stage(e, tmp.size() * 8, &d));
+            HIP_TRY(hipMemcpyAsync(d.p, tmp.data(), tmp.size() * 8, hipMemcpyHostToDevice,
+                                   e->stream));
+            HIP_TRY(gol::launch_rect_write(e->buf[e->cur] + word_off, (int64_t)e->stride,
+                                           (int64_t)(r.buf_row + (lo - r.glob_row)),
+                                           (int64_t)p.fcol, (int64_t)n, (int64_t)p.cols,
+                                           (const uint64_t*)d.p, (int64_t)pw, op, e->planes,
+                                           e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        }
+    }
+    return GOL_OK;
+}
+
+// Adds the pieces' live cells to counts (nby x nbx blocks, row stride cs).
+gol_status leaf_density(gol_engine* e, const std::vector<Region>& regs, uint64_t word_off,
+                        const RectPiece* pcs, size_t npc, uint64_t by, uint64_t bx, uint64_t nby,
+                        uint64_t nbx, uint32_t* counts, uint64_t cs)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    GOL_TRY(join_side_streams(e));
+    RectStage d;
+    const size_t bytes = (size_t)nby * nbx * sizeof(uint32_t);
+    GOL_TRY(rect_stage(e, bytes, &d));
+    HIP_TRY(hipMemsetAsync(d.p, 0, bytes, e->stream));
+    bool any = false;
+    for (size_t k = 0; k < npc; ++k) {
+        const RectPiece& p = pcs[k];
+        for (const auto& r : regs) {
+            uint64_t lo, hi;
+            if (!piece_rows(r, p, &lo, &hi) || !p.cols) continue;
+            any = true;
+            HIP_TRY(gol::launch_density(e->buf[e->cur] + word_off, (int64_t)e->stride,
+                                        (int64_t)(r.buf_row + (lo - r.glob_row)), (int64_t)p.fcol,
+                                        (int64_t)(hi - lo), (int64_t)p.cols,
+                                        (int64_t)(p.wrow + lo - p.frow), (int64_t)p.wcol,
+                                        (int64_t)by, (int64_t)bx, (uint32_t*)d.p, (int64_t)nbx,
+                                        e->planes, e->stream));
+        }
+    }
+    if (any) {
+        std::vector<uint32_t> tmp((size_t)nby * nbx);
+        HIP_TRY(hipMemcpyAsync(tmp.data(), d.p, bytes, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (uint64_t i = 0; i < nby; ++i)
+            for (uint64_t j = 0; j < nbx; ++j) counts[i * cs + j] += tmp[i * nbx + j];
+    }
+    return check_err(e);
+}
+
+// The call on an engine of gol_create / gol_create_rank / a group: a composite
+// engine hands the piece to every part, a leaf applies it to its own rows.
+static gol_status read_own(gol_engine* e, const RectPiece& p, uint64_t* words, uint64_t rs)
+{
+    for (auto* part : e->parts) GOL_TRY(read_own(part, p, words, rs));
+    if (!e->parts.empty()) return GOL_OK;
+    return leaf_read(e, e->user_regions, 0, &p, 1, words, rs);
+}
+
+static gol_status write_own(gol_engine* e, const RectPiece& p, const uint64_t* words, uint64_t rs,
+                            uint32_t op)
+{
+    for (auto* part : e->parts) GOL_TRY(write_own(part, p, words, rs, op));
+    if (!e->parts.empty()) return GOL_OK;
+    return leaf_write(e, e->user_regions, 0, &p, 1, words, rs, op);
+}
+
+static gol_status density_own(gol_engine* e, const RectPiece& p, uint64_t by, uint64_t bx,
+                              uint64_t nby, uint64_t nbx, uint32_t* counts, uint64_t cs)
+{
+    for (auto* part : e->parts) GOL_TRY(density_own(part, p, by, bx, nby, nbx, counts, cs));
+    if (!e->parts.empty()) return GOL_OK;
+    return leaf_density(e, e->user_regions, 0, &p, 1, by, bx, nby, nbx, counts, cs);
+}
+
+// Bounds of a rectangle: inside the field, or on a torus any start inside it and
+// at most one period each way.
+static gol_status rect_bounds(const gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw)
+{
+    const bool ok = e->inner ? (y < e->H && x < e->W && rh <= e->H && rw <= e->W)
+                             : (y <= e->H && rh <= e->H - y && x <= e->W && rw <= e->W - x);
+    if (ok) return GOL_OK;
+    return fail(GOL_EINVAL, "rectangle " + std::to_string(rh) + " x " + std::to_string(rw) +
+                                " at (" + std::to_string(y) + ", " + std::to_string(x) +
+                                ") is outside the " + std::to_string(e->H) + " x " +
+                                std::to_string(e->W) + (e->inner ? " torus" : " field"));
+}
+
+}  // namespace golh
+
+extern "C" {
+
+gol_status gol_read_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                         uint64_t* words, uint64_t rs)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    GOL_TRY(rect_bounds(e, y, x, rh, rw));
+    const uint64_t ww = (rw + 63) / 64;
+    if (rs < ww) return fail(GOL_EINVAL, "row stride smaller than ceil(rw/64)");
+    if (rh == 0 || rw == 0) return GOL_OK;
+    if (!words) return fail(GOL_EINVAL, "null argument");
+    // pad bits and the rows of a rank engine that are not its own read as 0
+    for (uint64_t i = 0; i < rh; ++i) std::memset(words + i * rs, 0, ww * 8);
+    if (e->inner) return torus_read_rect(e, y, x, rh, rw, words, rs);
+    return read_own(e, RectPiece{y, x, rh, rw, 0, 0}, words, rs);
+}
+
+gol_status gol_write_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                          const uint64_t* words, uint64_t rs, uint32_t op)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    if (op > GOL_RECT_CLEAR) return fail(GOL_EINVAL, "unknown rectangle op " + std::to_string(op));
+    if (e->sem == GOL_SEM_REF_STRIPES)
+        return fail(GOL_ESTATE, "REF_STRIPES keeps the stripes' overlap rows twice: a cell to "
+                                "write is ambiguous");
+    GOL_TRY(rect_bounds(e, y, x, rh, rw));
+    if (rs < (rw + 63) / 64) return fail(GOL_EINVAL, "row stride smaller than ceil(rw/64)");
+    if (rh == 0 || rw == 0) return GOL_OK;
+    if (!words) return fail(GOL_EINVAL, "null argument");
+    if (e->inner) return torus_write_rect(e, y, x, rh, rw, words, rs, op);
+    return write_own(e, RectPiece{y, x, rh, rw, 0, 0}, words, rs, op);
+}
+
+gol_status gol_density(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                       uint64_t by, uint64_t bx, uint32_t* counts, uint64_t cs)
+{
+    if (!e || !counts) return fail(GOL_EINVAL, "null argument");
+    if (by == 0 || bx == 0 || rh == 0 || rw == 0)
+        return fail(GOL_EINVAL, "density needs a window and blocks of at least one cell");
+    if (by > UINT32_MAX / bx) return fail(GOL_EINVAL, "density blocks of more than 2^32 - 1 cells");
+    GOL_TRY(rect_bounds(e, y, x, rh, rw));
+    const uint64_t nby = (rh + by - 1) / by, nbx = (rw + bx - 1) / bx;
+    if (cs < nbx) return fail(GOL_EINVAL, "row stride smaller than ceil(rw/bx)");
+    for (uint64_t i = 0; i < nby; ++i) std::memset(counts + i * cs, 0, nbx * sizeof(uint32_t));
+    if (e->inner) return torus_density(e, y, x, rh, rw, by, bx, nby, nbx, counts, cs);
+    return density_own(e, RectPiece{y, x, rh, rw, 0, 0}, by, bx, nby, nbx, counts, cs);
+}
+
+gol_status gol_rect_blit(const uint64_t* src, uint64_t src_stride, uint64_t sx, uint64_t* dst,
+                         uint64_t dst_stride, uint64_t dx, uint64_t rows, uint64_t cols,
+                         uint32_t op)
+{
+    if (op > GOL_RECT_CLEAR) return fail(GOL_EINVAL, "unknown rectangle op " + std::to_string(op));
+    if (sx > (1ull << 62) || dx > (1ull << 62) || cols > (1ull << 62))
+        return fail(GOL_EINVAL, "bit offsets too large");
+    if (src_stride < (sx + cols + 63) / 64 || dst_stride < (dx + cols + 63) / 64)
+        return fail(GOL_EINVAL, "row stride smaller than the words that hold the bits");
+    if (rows == 0 || cols == 0) return GOL_OK;
+    if (!src || !dst) return fail(GOL_EINVAL, "null argument");
+    for (uint64_t i = 0; i < rows; ++i)
+        gol_rect_blit_row(src + i * src_stride, (int64_t)sx, dst + i * dst_stride, (int64_t)dx,
+                          (int64_t)cols, op);
+    return GOL_OK;
 }
 
 

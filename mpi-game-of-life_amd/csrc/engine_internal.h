@@ -2,7 +2,7 @@
 // translation units: the engine struct, the stripe geometry, the error macros and
 // the internal functions each unit exports to the others.
 //   engine.cpp   C ABI lifecycle, load/store, single-field and resident steps,
-//                launches and timing, digests, plan queries
+//                launches and timing, digests, region I/O, plan queries
 //   plan.cpp     launch planning: column layout, rows per wavefront, age-skewed
 //                blocks, hand-off vs classic, the plan autotuner
 //   stripes.cpp  multi-GPU stripes: rank geometry and halo rounds, the exchange
@@ -32,6 +32,7 @@
 #include "../../include/gol.h"
 #include "bitlayout.h"
 #include "life_internal.h"
+#include "rect_blit.h"
 
 namespace golh __attribute__((visibility("hidden"))) {
 
@@ -361,6 +362,9 @@ struct gol_engine {
 
     unsigned long long* d_acc = nullptr;
     int* d_flag = nullptr;  // ASCII codec error flag
+    // region I/O: device staging kept between calls (engine.cpp rect_stage)
+    char* rect_stage = nullptr;
+    size_t rect_stage_bytes = 0;
 
     // single-stream engines replay a captured hipGraph of the launch sequence of a
     // gol_step(gens) call (keyed by gens and the starting buffer), so a step of
@@ -412,6 +416,25 @@ gol_status join_side_streams(gol_engine* e);
 gol_status quiesce(gol_engine* e);
 gol_status check_err(gol_engine* e);
 
+// Region I/O (gol_read_rect / gol_write_rect / gol_density).  A piece is a
+// non-wrapping rectangle in a leaf engine's field coordinates -- rows [frow, frow +
+// rows) x columns [fcol, fcol + cols) -- whose first cell is cell (wrow, wcol) of the
+// caller's window.  The leaf_ functions apply pieces to the rows of `regs` (field row
+// -> buffer row, as user_regions) of the view that starts word_off words into each
+// buffer row (0, or a torus interior's ghost words).  leaf_read fills only the
+// pieces' bits of `words`; leaf_density adds to `counts`.
+struct RectPiece {
+    uint64_t frow, fcol, rows, cols, wrow, wcol;
+};
+gol_status leaf_read(gol_engine* e, const std::vector<Region>& regs, uint64_t word_off,
+                     const RectPiece* pcs, size_t npc, uint64_t* words, uint64_t rs);
+gol_status leaf_write(gol_engine* e, const std::vector<Region>& regs, uint64_t word_off,
+                      const RectPiece* pcs, size_t npc, const uint64_t* words, uint64_t rs,
+                      uint32_t op);
+gol_status leaf_density(gol_engine* e, const std::vector<Region>& regs, uint64_t word_off,
+                        const RectPiece* pcs, size_t npc, uint64_t by, uint64_t bx, uint64_t nby,
+                        uint64_t nbx, uint32_t* counts, uint64_t cs);
+
 // ---- plan.cpp
 struct URect {
     int64_t r0, r1, q0, q1;  // rows [r0, r1) x lane groups [q0, q1)
@@ -443,6 +466,13 @@ gol_status torus_store_ascii(gol_engine* e, char* buf, size_t len);
 gol_status torus_init_random(gol_engine* e, uint64_t seed);
 gol_status torus_digest_rows(gol_engine* e, uint64_t row0, uint64_t rows, uint64_t* live,
                              uint64_t* hash);
+gol_status torus_read_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                           uint64_t* words, uint64_t rs);
+gol_status torus_write_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                            const uint64_t* words, uint64_t rs, uint32_t op);
+gol_status torus_density(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                         uint64_t by, uint64_t bx, uint64_t nby, uint64_t nbx, uint32_t* counts,
+                         uint64_t cs);
 
 // ---- stripes.cpp
 uint32_t pick_depth(uint32_t K, uint64_t remaining);

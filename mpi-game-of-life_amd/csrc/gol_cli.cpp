@@ -19,6 +19,12 @@
 // output.txt format; one engine on one GPU, so not with --ref-ranks, nor with
 // --gpus or --stripes above 1.  --halo-depth then sets the generations per wrap
 // round.
+// --paste FILE@Y,X[:set|or|xor|clear] combines the cells of FILE (data.txt format:
+// lines of '0'/'1', its height and width are those of its lines) into the field
+// with its first cell at row Y, column X (gol_write_rect; default set).  Repeatable,
+// applied in order after data.txt is loaded and before the first generation.
+// --window Y,X,H,W writes only that window to output.txt (gol_read_rect): H lines of
+// W cells; the file is truncated to them.  With --torus either may cross the seams.
 //
 // Deviation: where the reference prints an error and continues with
 // uninitialised values (:206) or an unopened file (:186), this program exits
@@ -32,6 +38,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -76,7 +83,11 @@ void usage()
     std::cerr << "usage: gol [--dir DIR] [--ref-ranks P] [--rule ref|conway|B3/S23]\n"
                  "           [--tb-depth K] [--rows-per-wave N] [--device D]\n"
                  "           [--gpus G] [--stripes S] [--halo-depth H] [--torus]\n"
+                 "           [--paste FILE@Y,X[:set|or|xor|clear]]... [--window Y,X,H,W]\n"
                  "Reads grid_size_data.txt and data.txt, writes output.txt.\n"
+                 "--paste: combine the cells of FILE (lines of 0/1) into the loaded field at\n"
+                 "         row Y, column X before stepping (default set); repeatable.\n"
+                 "--window: output.txt holds only the H x W window at row Y, column X.\n"
                  "--torus: the field's opposite edges are joined (periodic boundary);\n"
                  "         not with --ref-ranks, nor with --gpus / --stripes above 1.\n";
 }
@@ -96,6 +107,80 @@ bool read_file(const std::string& path, size_t need, std::vector<char>& out)
     return got == need;
 }
 
+// --paste FILE@Y,X[:op]
+struct Paste {
+    std::string file;
+    uint64_t y = 0, x = 0, h = 0, w = 0;
+    uint32_t op = GOL_RECT_SET;
+    std::vector<uint64_t> words;  // packed, ceil(w/64) per row
+};
+
+bool parse_u64s(const std::string& s, uint64_t* v, int n)
+{
+    const char* p = s.c_str();
+    for (int i = 0; i < n; ++i) {
+        if (*p < '0' || *p > '9') return false;
+        char* end = nullptr;
+        v[i] = std::strtoull(p, &end, 10);
+        p = end;
+        if (i + 1 < n) {
+            if (*p != ',') return false;
+            ++p;
+        }
+    }
+    return *p == 0;
+}
+
+bool parse_paste(const std::string& a, Paste* out)
+{
+    const size_t at = a.rfind('@');
+    if (at == std::string::npos || at == 0) return false;
+    out->file = a.substr(0, at);
+    std::string pos = a.substr(at + 1);
+    const size_t colon = pos.find(':');
+    if (colon != std::string::npos) {
+        const std::string op = pos.substr(colon + 1);
+        if (op == "set") out->op = GOL_RECT_SET;
+        else if (op == "or") out->op = GOL_RECT_OR;
+        else if (op == "xor") out->op = GOL_RECT_XOR;
+        else if (op == "clear") out->op = GOL_RECT_CLEAR;
+        else return false;
+        pos = pos.substr(0, colon);
+    }
+    uint64_t v[2];
+    if (!parse_u64s(pos, v, 2)) return false;
+    out->y = v[0];
+    out->x = v[1];
+    return true;
+}
+
+// Reads a paste file: equal lines of '0' / '1', each ended by '\n' (the last one may
+// lack it).  Returns an error message, empty on success.
+std::string load_paste(Paste* p)
+{
+    std::ifstream f(p->file, std::ios::binary);
+    if (!f) return "cannot open";
+    const std::string txt((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    size_t pos = 0;
+    while (pos < txt.size()) {
+        size_t nl = txt.find('\n', pos);
+        if (nl == std::string::npos) nl = txt.size();
+        const uint64_t len = nl - pos;
+        if (p->h == 0) p->w = len;
+        if (len != p->w || len == 0) return "lines of unequal or zero length";
+        const uint64_t wq = (p->w + 63) / 64;
+        p->words.resize((size_t)((p->h + 1) * wq), 0);
+        for (uint64_t j = 0; j < len; ++j) {
+            const char c = txt[pos + j];
+            if (c != '0' && c != '1') return "a byte other than '0' or '1'";
+            if (c == '1') p->words[(size_t)(p->h * wq + j / 64)] |= 1ull << (j & 63);
+        }
+        ++p->h;
+        pos = nl + 1;
+    }
+    return p->h ? "" : "empty file";
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -103,7 +188,9 @@ int main(int argc, char** argv)
     const auto t0 = std::chrono::steady_clock::now();  // MPI_Wtime() at :199
     std::string dir = ".";
     int gpus = 0, stripes = 0;
-    bool torus = false, ref_ranks = false;
+    bool torus = false, ref_ranks = false, window = false;
+    uint64_t win[4] = {0, 0, 0, 0};  // Y, X, H, W
+    std::vector<Paste> pastes;
     gol_config cfg;
     gol_config_init(&cfg);
     for (int i = 1; i < argc; ++i) {
@@ -132,7 +219,20 @@ int main(int argc, char** argv)
         else if (a == "--gpus") gpus = (int)std::strtol(next().c_str(), nullptr, 10);
         else if (a == "--stripes") stripes = (int)std::strtol(next().c_str(), nullptr, 10);
         else if (a == "--halo-depth") cfg.halo_depth = (uint32_t)std::strtoul(next().c_str(), nullptr, 10);
-        else if (a == "-h" || a == "--help") {
+        else if (a == "--paste") {
+            Paste p;
+            if (!parse_paste(next(), &p)) {
+                std::cerr << "bad --paste, want FILE@Y,X[:set|or|xor|clear]\n";
+                return 2;
+            }
+            pastes.push_back(p);
+        } else if (a == "--window") {
+            if (!parse_u64s(next(), win, 4)) {
+                std::cerr << "bad --window, want Y,X,H,W\n";
+                return 2;
+            }
+            window = true;
+        } else if (a == "-h" || a == "--help") {
             usage();
             return 0;
         } else {
@@ -175,6 +275,42 @@ int main(int argc, char** argv)
         return 1;
     }
 
+    for (auto& p : pastes) {
+        const std::string err = load_paste(&p);
+        if (!err.empty()) {
+            std::cerr << "gol error " << (int)GOL_EINVAL << ": paste file " << p.file << ": " << err
+                      << std::endl;
+            return 1;
+        }
+    }
+    // region I/O on the engines of either path below (a group: every member takes
+    // its own rows; the members' windows are OR-ed)
+    auto paste_all = [&](const std::vector<gol_engine*>& es) {
+        for (const auto& p : pastes)
+            for (auto* e : es) {
+                const gol_status st = gol_write_rect(e, p.y, p.x, p.h, p.w, p.words.data(),
+                                                     (p.w + 63) / 64, p.op);
+                if (st != GOL_OK) return st;
+            }
+        return GOL_OK;
+    };
+    auto read_window = [&](const std::vector<gol_engine*>& es, std::vector<char>& txt) {
+        const uint64_t ww = (win[3] + 63) / 64;
+        std::vector<uint64_t> acc((size_t)(win[2] * ww), 0), one(acc.size(), 0);
+        for (auto* e : es) {
+            const gol_status st = gol_read_rect(e, win[0], win[1], win[2], win[3], one.data(), ww);
+            if (st != GOL_OK) return st;
+            for (size_t i = 0; i < acc.size(); ++i) acc[i] |= one[i];
+        }
+        txt.assign((size_t)(win[2] * (win[3] + 1)), '\n');
+        for (uint64_t i = 0; i < win[2]; ++i)
+            for (uint64_t j = 0; j < win[3]; ++j)
+                txt[(size_t)(i * (win[3] + 1) + j)] =
+                    ((acc[(size_t)(i * ww + j / 64)] >> (j & 63)) & 1) ? '1' : '0';
+        return GOL_OK;
+    };
+    const bool edits = !pastes.empty() || window;
+
     std::vector<char> out(bytes);
     if (gpus > 0 || stripes > 0) {
         if (cfg.semantics != GOL_SEM_GLOBAL) {
@@ -188,7 +324,7 @@ int main(int argc, char** argv)
             return 1;
         }
     }
-    if (epochs == 0) {
+    if (epochs == 0 && !edits) {
         // zero generations: the reference writes the input bytes back (:157-164)
         out = data;
     } else if (stripes > 0) {
@@ -203,8 +339,10 @@ int main(int argc, char** argv)
             st = gol_load_ascii(es[(size_t)r], data.data() + r0 * (uint64_t)(w + 1),
                                 n * (uint64_t)(w + 1));
         }
-        if (st == GOL_OK) st = gol_group_step(es.data(), stripes, (uint64_t)epochs);
-        for (int r = 0; r < stripes && st == GOL_OK; ++r) {
+        if (st == GOL_OK) st = paste_all(es);
+        if (st == GOL_OK && epochs > 0) st = gol_group_step(es.data(), stripes, (uint64_t)epochs);
+        if (st == GOL_OK && window) st = read_window(es, out);
+        for (int r = 0; r < stripes && st == GOL_OK && !window; ++r) {
             uint64_t r0 = 0, n = 0;
             gol_rank_rows((uint64_t)h, stripes, r, &r0, &n);
             st = gol_store_ascii(es[(size_t)r], out.data() + r0 * (uint64_t)(w + 1),
@@ -217,9 +355,10 @@ int main(int argc, char** argv)
         gol_engine* e = nullptr;
         gol_status st = gol_create((uint64_t)h, (uint64_t)w, &cfg, &e);
         if (st == GOL_OK) st = gol_load_ascii(e, data.data(), data.size());
-        if (st == GOL_OK) st = gol_step(e, (uint64_t)epochs);
+        if (st == GOL_OK) st = paste_all({e});
+        if (st == GOL_OK && epochs > 0) st = gol_step(e, (uint64_t)epochs);
         if (st == GOL_OK) st = gol_sync(e);
-        if (st == GOL_OK) st = gol_store_ascii(e, out.data(), out.size());
+        if (st == GOL_OK) st = window ? read_window({e}, out) : gol_store_ascii(e, out.data(), out.size());
         if (st != GOL_OK) {
             std::cerr << "gol error " << (int)st << ": " << gol_last_error() << std::endl;
             gol_destroy(e);
@@ -235,10 +374,18 @@ int main(int argc, char** argv)
         std::cerr << "Error opening the file for writing." << std::endl;  // :186
         return 1;
     }
-    const size_t chunk = (size_t)(h / P) * (size_t)(w + 1);
-    for (uint32_t r = 0; r < P; ++r) {
+    // (--window: the file holds the window alone, written by "rank" 0)
+    if (window && ::ftruncate(fd, 0) != 0) {
+        std::cerr << "Error writing output.txt." << std::endl;
+        ::close(fd);
+        return 1;
+    }
+    const uint32_t writers = window ? 1 : P;
+    const size_t total = window ? out.size() : bytes;
+    const size_t chunk = window ? total : (size_t)(h / P) * (size_t)(w + 1);
+    for (uint32_t r = 0; r < writers; ++r) {
         const size_t off = (size_t)r * chunk;
-        const size_t len = (r == P - 1) ? bytes - off : chunk;
+        const size_t len = (r == writers - 1) ? total - off : chunk;
         size_t done = 0;
         while (done < len) {
             ssize_t n = ::pwrite(fd, out.data() + off + done, len - done, (off_t)(off + done));

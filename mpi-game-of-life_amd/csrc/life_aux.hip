@@ -1,11 +1,12 @@
 // life_aux.hip -- memory-bound helper kernels (synthetic init, digest, ASCII
-// codec) and the depth dispatch of the stencil kernel (life_stencil.h, one
-// translation unit per depth: life_tb_d<K>.hip).
+// codec, torus wrap, region I/O) and the depth dispatch of the stencil kernel
+// (life_stencil.h, one translation unit per depth: life_tb_d<K>.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bitlayout.h"
 #include "life_internal.h"
+#include "rect_blit.h"
 #include "torus_wrap.h"
 
 namespace gol {
@@ -259,6 +260,182 @@ __global__ __launch_bounds__(256) void torus_wrap_kernel(uint64_t* buf, int64_t 
     }
 }
 
+// ---- Region I/O (gol_read_rect / gol_write_rect / gol_density; rect_blit.h) ----
+// The three kernels see one non-wrapping piece of a rectangle: `rows` buffer rows
+// from row_base on, field columns [x, x + cols) of a view `buf` whose word 0 is
+// field column 0 (a torus interior: the inner buffer + its ghost words).  No bit at
+// or beyond column x + cols is read for its value or changed.
+
+// canonical word q of a stored row
+template <int NP>
+__device__ __forceinline__ uint64_t load_canonical(const uint64_t* row, int64_t q)
+{
+    constexpr int G = NP / 2;
+    const int64_t g = q / G;
+    uint64_t s[2] = {0, 0}, c[2] = {0, 0};
+#pragma unroll
+    for (int j = 0; j < G; ++j) s[j] = row[g * G + j];
+    gol_join_group(s, c, NP);
+    return (q - g * G) ? c[1] : c[0];
+}
+
+// One thread per word of the compact staging window dst (rows x ceil(cols/64)
+// words): bit j of word dq of row i = field column x + 64 dq + j, 0 from cols on.
+template <int NP>
+__global__ __launch_bounds__(256) void rect_read_kernel(const uint64_t* buf, int64_t stride,
+                                                        int64_t row_base, int64_t x, int64_t rows,
+                                                        int64_t cols, uint64_t* dst,
+                                                        int64_t dst_stride)
+{
+    const int64_t ww = (cols + 63) >> 6;
+    const int64_t total = rows * ww;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = k / ww, dq = k - i * ww;
+        const uint64_t* row = buf + (row_base + i) * stride;
+        uint64_t m;
+        dst[i * dst_stride + dq] = gol_rect_word(
+            [row](int64_t q) { return load_canonical<NP>(row, q); }, x, 0, cols, dq, &m);
+    }
+}
+
+// One thread per lane group of the field that holds a column of the piece, so no
+// two threads touch the same word.  src is the compact staged window (bit 0 of a
+// row = field column x).  A group wholly inside the piece under SET is not loaded.
+template <int NP>
+__global__ __launch_bounds__(256) void rect_write_kernel(uint64_t* buf, int64_t stride,
+                                                         int64_t row_base, int64_t x, int64_t rows,
+                                                         int64_t cols, const uint64_t* src,
+                                                         int64_t src_stride, uint32_t op)
+{
+    constexpr int G = NP / 2;
+    const int64_t g0 = x / (64 * G), ngr = (x + cols - 1) / (64 * G) - g0 + 1;
+    const int64_t total = rows * ngr;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < total;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = k / ngr, gq = g0 + (k - i * ngr);
+        const uint64_t* srow = src + i * src_stride;
+        uint64_t* grp = buf + (row_base + i) * stride + gq * G;
+        uint64_t v[2] = {0, 0}, m[2] = {0, 0}, c[2] = {0, 0}, s[2] = {0, 0};
+        bool full = true;
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            v[j] = gol_rect_word([srow](int64_t q) { return srow[q]; }, 0, x, cols, gq * G + j,
+                                 &m[j]);
+            full &= m[j] == ~0ull;
+        }
+        if (op == GOL_RECT_OP_SET && full) {
+            c[0] = v[0];
+            c[1] = v[1];
+        } else {
+#pragma unroll
+            for (int j = 0; j < G; ++j) s[j] = grp[j];
+            gol_join_group(s, c, NP);
+#pragma unroll
+            for (int j = 0; j < G; ++j) c[j] = gol_rect_merge(c[j], v[j], m[j], op);
+        }
+        gol_split_group(c, s, NP);
+#pragma unroll
+        for (int j = 0; j < G; ++j) grp[j] = s[j];
+    }
+}
+
+// bits [lo, hi) of the row that fall into the word starting at bit wb
+__device__ __forceinline__ uint64_t range_mask(int64_t lo, int64_t hi, int64_t wb)
+{
+    const int64_t a = lo > wb ? lo - wb : 0, b = hi < wb + 64 ? hi - wb : 64;
+    if (b <= a) return 0;
+    return (b - a == 64 ? ~0ull : (1ull << (b - a)) - 1ull) << a;
+}
+
+// Live cells per by x bx block.  The piece's first cell is window cell (wrow0,
+// wcol0); block (bi, bj) holds window rows [bi by, (bi + 1) by) and columns
+// [bj bx, (bj + 1) bx), and its cells in this piece are added to
+// counts[bi * cstride + bj].  One wavefront per work item = 64 consecutive lane
+// groups x up to rpi rows of one block row: a lane keeps its group and therefore
+// its block, loads one stored group per row (the wavefront 64 consecutive ones) and
+// counts it without a join, the stored format being a bit permutation: a group cut
+// by the piece's edge is masked with the split form of its column mask.  The lanes
+// of one block then add up with shuffles (their keys rise along the wavefront, so
+// equal keys are neighbours) and the first of them adds the sum to the block.  A
+// group whose columns fall into several blocks (bx below the group's width, or a
+// block edge inside it) is joined and counted per block instead.
+template <int NP>
+__global__ __launch_bounds__(256) void density_kernel(const uint64_t* buf, int64_t stride,
+                                                      int64_t row_base, int64_t x, int64_t rows,
+                                                      int64_t cols, int64_t wrow0, int64_t wcol0,
+                                                      int64_t by, int64_t bx, uint32_t* counts,
+                                                      int64_t cstride, int64_t rpi)
+{
+    constexpr int G = NP / 2;
+    constexpr int64_t GC = 64 * G;
+    const int lane = threadIdx.x & 63;
+    const int64_t g0 = x / GC, g1 = (x + cols - 1) / GC;
+    const int64_t nchunk = (g1 - g0 + 64) / 64;
+    const int64_t bi0 = wrow0 / by, nbr = (wrow0 + rows - 1) / by - bi0 + 1;
+    const int64_t ppb = (by + rpi - 1) / rpi;
+    const int64_t total = nbr * ppb * nchunk;
+    const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t k = wave0; k < total; k += nwaves) {
+        const int64_t chunk = k % nchunk, t = k / nchunk;
+        const int64_t bi = bi0 + t / ppb, p = t % ppb;
+        // window rows of this item, clipped to the block row and the piece
+        int64_t r0 = bi * by + p * rpi, r1 = r0 + rpi;
+        if (r1 > (bi + 1) * by) r1 = (bi + 1) * by;
+        if (r0 < wrow0) r0 = wrow0;
+        if (r1 > wrow0 + rows) r1 = wrow0 + rows;
+        if (r1 <= r0) continue;  // (uniform over the wavefront)
+        const int64_t gq = g0 + chunk * 64 + lane;
+        const bool on = gq <= g1;
+        // field columns [c0, c1) of this group inside the piece, and their blocks
+        const int64_t c0 = on ? (gq * GC > x ? gq * GC : x) : 0;
+        const int64_t c1 = on ? ((gq + 1) * GC < x + cols ? (gq + 1) * GC : x + cols) : 0;
+        const int64_t bj0 = on ? (wcol0 + c0 - x) / bx : 0;
+        const int64_t bj1 = on ? (wcol0 + c1 - 1 - x) / bx : 0;
+        const bool single = on && bj0 == bj1;
+        const uint64_t* grp = buf + (row_base + (r0 - wrow0)) * stride + gq * G;
+        uint32_t val = 0;
+        if (single) {
+            uint64_t cm[2] = {0, 0}, sm[2] = {0, 0};
+#pragma unroll
+            for (int j = 0; j < G; ++j) cm[j] = range_mask(c0, c1, (gq * G + j) * 64);
+            gol_split_group(cm, sm, NP);
+#pragma unroll 4
+            for (int64_t r = 0; r < r1 - r0; ++r) {
+#pragma unroll
+                for (int j = 0; j < G; ++j) val += (uint32_t)__popcll(grp[r * stride + j] & sm[j]);
+            }
+        } else if (on) {
+            for (int64_t r = 0; r < r1 - r0; ++r) {
+                uint64_t s[2] = {0, 0}, c[2] = {0, 0};
+#pragma unroll
+                for (int j = 0; j < G; ++j) s[j] = grp[r * stride + j];
+                gol_join_group(s, c, NP);
+                for (int64_t bj = bj0; bj <= bj1; ++bj) {
+                    // field columns of block bj inside this group
+                    const int64_t lo = x - wcol0 + bj * bx, hi = lo + bx;
+                    const int64_t a = lo > c0 ? lo : c0, b = hi < c1 ? hi : c1;
+                    uint32_t n = 0;
+#pragma unroll
+                    for (int j = 0; j < G; ++j)
+                        n += (uint32_t)__popcll(c[j] & range_mask(a, b, (gq * G + j) * 64));
+                    if (n) atomicAdd(&counts[bi * cstride + bj], n);
+                }
+            }
+        }
+        long long key = single ? (long long)bj0 : -1ll;
+        for (int off = 1; off < 64; off <<= 1) {
+            const long long ok = __shfl_down(key, off);
+            const uint32_t ov = __shfl_down(val, off);
+            if (lane + off < 64 && ok == key) val += ov;
+        }
+        const long long prev = __shfl_up(key, 1);
+        if (key >= 0 && val && (lane == 0 || prev != key))
+            atomicAdd(&counts[bi * cstride + key], val);
+    }
+}
+
 dim3 grid_for(int64_t items, int64_t per_block, int64_t cap)
 {
     int64_t blocks = (items + per_block - 1) / per_block;
@@ -336,6 +513,63 @@ hipError_t launch_torus_wrap(uint64_t* buf, int64_t stride, int64_t h, int64_t w
     const int64_t total = 2 * G * wq_pad + h * (wq_pad - (w >> 6));
     hipLaunchKernelGGL(torus_wrap_kernel, grid_for(total, 256, 8192), dim3(256), 0, s, buf, stride,
                        h, w, G, Gx, wq_pad);
+    return hipGetLastError();
+}
+
+// Region I/O launchers: one non-wrapping piece each (see the kernels above).
+hipError_t launch_rect_read(const uint64_t* buf, int64_t stride, int64_t row_base, int64_t x,
+                            int64_t rows, int64_t cols, uint64_t* dst, int64_t dst_stride,
+                            int planes, hipStream_t s)
+{
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    const dim3 grid = grid_for(rows * ((cols + 63) / 64), 256, 8192);
+    if (planes == 4)
+        hipLaunchKernelGGL(rect_read_kernel<4>, grid, dim3(256), 0, s, buf, stride, row_base, x,
+                           rows, cols, dst, dst_stride);
+    else
+        hipLaunchKernelGGL(rect_read_kernel<2>, grid, dim3(256), 0, s, buf, stride, row_base, x,
+                           rows, cols, dst, dst_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_rect_write(uint64_t* buf, int64_t stride, int64_t row_base, int64_t x,
+                             int64_t rows, int64_t cols, const uint64_t* src, int64_t src_stride,
+                             uint32_t op, int planes, hipStream_t s)
+{
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (op > GOL_RECT_OP_CLEAR) return hipErrorInvalidValue;
+    const int64_t gc = 32 * planes;
+    const dim3 grid = grid_for(rows * ((x + cols - 1) / gc - x / gc + 1), 256, 8192);
+    if (planes == 4)
+        hipLaunchKernelGGL(rect_write_kernel<4>, grid, dim3(256), 0, s, buf, stride, row_base, x,
+                           rows, cols, src, src_stride, op);
+    else
+        hipLaunchKernelGGL(rect_write_kernel<2>, grid, dim3(256), 0, s, buf, stride, row_base, x,
+                           rows, cols, src, src_stride, op);
+    return hipGetLastError();
+}
+
+hipError_t launch_density(const uint64_t* buf, int64_t stride, int64_t row_base, int64_t x,
+                          int64_t rows, int64_t cols, int64_t wrow0, int64_t wcol0, int64_t by,
+                          int64_t bx, uint32_t* counts, int64_t cstride, int planes,
+                          hipStream_t s)
+{
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (by <= 0 || bx <= 0) return hipErrorInvalidValue;
+    // rows per work item: up to 32 of one block row (a lane adds 32 x 64 x planes / 2
+    // cells at most, and tall blocks still split into enough wavefronts)
+    const int64_t rpi = by < 32 ? by : 32;
+    const int64_t gc = 32 * planes;
+    const int64_t nchunk = ((x + cols - 1) / gc - x / gc + 64) / 64;
+    const int64_t nbr = (wrow0 + rows - 1) / by - wrow0 / by + 1;
+    const int64_t items = nbr * ((by + rpi - 1) / rpi) * nchunk;
+    const dim3 grid = grid_for(items, 4, 8192);
+    if (planes == 4)
+        hipLaunchKernelGGL(density_kernel<4>, grid, dim3(256), 0, s, buf, stride, row_base, x,
+                           rows, cols, wrow0, wcol0, by, bx, counts, cstride, rpi);
+    else
+        hipLaunchKernelGGL(density_kernel<2>, grid, dim3(256), 0, s, buf, stride, row_base, x,
+                           rows, cols, wrow0, wcol0, by, bx, counts, cstride, rpi);
     return hipGetLastError();
 }
 

@@ -292,4 +292,22 @@ hipError_t launch_digest(const uint64_t* buf, int64_t stride, int64_t wq, int64_
 hipError_t launch_torus_wrap(uint64_t* buf, int64_t stride, int64_t h, int64_t w, int64_t G,
                              int64_t Gx, hipStream_t s);
 
+// Region I/O (gol_read_rect / gol_write_rect / gol_density), one non-wrapping piece
+// per launch: buffer rows [row_base, row_base + rows) x field columns [x, x + cols)
+// of the view `buf` (word 0 = field column 0).  Read fills a compact staging window
+// (bit 0 of a row = column x, 0 from cols on); write merges one under op
+// (gol_rect_op); density adds the piece's live cells per by x bx block of the
+// window whose cell (wrow0, wcol0) is the piece's first, into counts[bi * cstride +
+// bj] (zeroed by the caller).
+hipError_t launch_rect_read(const uint64_t* buf, int64_t stride, int64_t row_base, int64_t x,
+                            int64_t rows, int64_t cols, uint64_t* dst, int64_t dst_stride,
+                            int planes, hipStream_t s);
+hipError_t launch_rect_write(uint64_t* buf, int64_t stride, int64_t row_base, int64_t x,
+                             int64_t rows, int64_t cols, const uint64_t* src, int64_t src_stride,
+                             uint32_t op, int planes, hipStream_t s);
+hipError_t launch_density(const uint64_t* buf, int64_t stride, int64_t row_base, int64_t x,
+                          int64_t rows, int64_t cols, int64_t wrow0, int64_t wcol0, int64_t by,
+                          int64_t bx, uint32_t* counts, int64_t cstride, int planes,
+                          hipStream_t s);
+
 }  // namespace gol

@@ -258,6 +258,54 @@ gol_status torus_digest_rows(gol_engine* e, uint64_t row0, uint64_t rows, uint64
     return check_err(in);
 }
 
+// Region I/O: window cell (i, j) is interior cell ((y + i) mod h, (x + j) mod w), so
+// a rectangle splits at the seams into at most 2 x 2 non-wrapping pieces of the
+// interior, which sits at buffer row tG, word tGx of the inner engine.
+static size_t torus_pieces(const gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                           RectPiece out[4])
+{
+    const uint64_t h0 = std::min(rh, e->H - y), w0 = std::min(rw, e->W - x);
+    const uint64_t rows[2][3] = {{y, h0, 0}, {0, rh - h0, h0}};  // start, count, window row
+    const uint64_t cols[2][3] = {{x, w0, 0}, {0, rw - w0, w0}};
+    size_t n = 0;
+    for (const auto& r : rows)
+        for (const auto& c : cols)
+            if (r[1] && c[1]) out[n++] = RectPiece{r[0], c[0], r[1], c[1], r[2], c[2]};
+    return n;
+}
+
+static std::vector<Region> interior_regions(const gol_engine* e)
+{
+    return {Region{e->tG, 0, 0, e->H}};
+}
+
+gol_status torus_read_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                           uint64_t* words, uint64_t rs)
+{
+    RectPiece pcs[4];
+    const size_t n = torus_pieces(e, y, x, rh, rw, pcs);
+    return leaf_read(e->inner, interior_regions(e), e->tGx, pcs, n, words, rs);
+}
+
+gol_status torus_write_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                            const uint64_t* words, uint64_t rs, uint32_t op)
+{
+    // (the ghosts go stale; the wrap at the start of the next round rewrites them)
+    RectPiece pcs[4];
+    const size_t n = torus_pieces(e, y, x, rh, rw, pcs);
+    return leaf_write(e->inner, interior_regions(e), e->tGx, pcs, n, words, rs, op);
+}
+
+gol_status torus_density(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
+                         uint64_t by, uint64_t bx, uint64_t nby, uint64_t nbx, uint32_t* counts,
+                         uint64_t cs)
+{
+    RectPiece pcs[4];
+    const size_t n = torus_pieces(e, y, x, rh, rw, pcs);
+    return leaf_density(e->inner, interior_regions(e), e->tGx, pcs, n, by, bx, nby, nbx, counts,
+                        cs);
+}
+
 }  // namespace golh
 
 extern "C" {
