@@ -236,10 +236,17 @@ gol_status gol_reset_timing(gol_engine* e);
  * returns how many of those did so without stage logic: a unit whose neighbourhood
  * ended the launch before quiet copies its rows into the output buffer
  * (copy-through, on wherever the skip is; GOL_DEV_COPY_THROUGH=0 at create turns it
- * off and leaves the skip alone).  Any out pointer may be NULL.  Composite engines,
- * group members and rank engines of more than one rank keep no counters: all 0. */
+ * off and leaves the skip alone).  gol_activity_probed returns how many computed
+ * units were found still by the first launch of a gol_step, which has no history:
+ * such a unit runs one generation over the rows it streams and, where that changes
+ * nothing within depth - 1 cells of its rows, stores its input rows without the
+ * other generations' stage logic (the still probe, on wherever the skip is;
+ * GOL_DEV_STILL_PROBE=0 at create turns it off); these units are not counted as
+ * copied.  Any out pointer may be NULL.  Composite engines, group members and rank
+ * engines of more than one rank keep no counters: all 0. */
 gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units);
 gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units);
+gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units);
 
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */

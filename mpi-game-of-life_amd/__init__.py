@@ -39,7 +39,7 @@ EXPORTS = [
     "gol_plan_resident", "gol_plan_skew", "gol_plan_columns", "gol_plan_tuning",
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
-    "gol_activity_copied", "gol_torus_geometry", "gol_torus_pad",
+    "gol_activity_copied", "gol_activity_probed", "gol_torus_geometry", "gol_torus_pad",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
 ]
 
@@ -200,6 +200,7 @@ def lib():
                                  ctypes.POINTER(PlanSummary)]
     L.gol_activity.argtypes = [vp, pu64, pu64]
     L.gol_activity_copied.argtypes = [vp, pu64]
+    L.gol_activity_probed.argtypes = [vp, pu64]
     L.gol_plan_neighbours.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, vp, u64,
                                       vp, u64, pu64, pu64]
     L.gol_torus_geometry.argtypes = [u64, u64, ctypes.POINTER(Config), ctypes.POINTER(u32),
@@ -220,7 +221,7 @@ def lib():
                  "gol_create_rank_transport", "gol_round_schedule", "gol_plan_tuning",
                  "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
                  "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity",
-                 "gol_plan_neighbours", "gol_activity_copied"]:
+                 "gol_plan_neighbours", "gol_activity_copied", "gol_activity_probed"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -553,6 +554,14 @@ class Engine:
         stage logic (copy-through; gol_activity_copied)."""
         c = ctypes.c_uint64()
         _check(lib().gol_activity_copied(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_probed(self):
+        """Units counted as computed by activity() that a step's first launch found
+        still after one generation and stored as they were (the still probe;
+        gol_activity_probed).  Not counted in activity_copied()."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_probed(self._h, ctypes.byref(c)))
         return c.value
 
     def timing(self):

@@ -298,6 +298,9 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
         e->through_on = !e->act_on ? 0 : !t ? 2 : std::max(0, std::min(2, std::atoi(t)));
         const char* x = std::getenv("GOL_DEV_STILL_EXIT");
         e->still_on = e->act_on && !(x && std::atoi(x) == 0);
+        // the still probe of a step's first launch (GOL_DEV_STILL_PROBE=0 = off)
+        const char* pr = std::getenv("GOL_DEV_STILL_PROBE");
+        e->probe_on = e->act_on && !(pr && std::atoi(pr) == 0);
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return GOL_OK;
@@ -641,6 +644,8 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             a.nb_off = p.d_nb;
             a.nb_ids = p.d_nb + p.nb_off.size();
             a.no_hist = e->act_launch == 0 ? 1 : 0;
+            a.probe = (a.no_hist && e->probe_on) ? 1 : 0;
+            a.probed = e->d_streak + 5 * e->act_units + 2;
             a.through = e->through_on >= 1 ? 1 : 0;
             a.busy = e->still_on ? e->d_streak + 5 * e->act_units : nullptr;
             a.launch_idx = e->act_launch;
@@ -1811,7 +1816,34 @@ gol_status gol_reset_timing(gol_engine* e)
         // skipped as a whole
         HIP_TRY(hipMemsetAsync(e->d_streak + 2 * e->act_units, 0,
                                (3 * (size_t)e->act_units + 1) * sizeof(uint32_t), e->stream));
+        // the probed counters, behind the two words of the one-load exit
+        HIP_TRY(hipMemsetAsync(e->d_streak + 5 * e->act_units + 2, 0,
+                               (size_t)e->act_units * sizeof(uint32_t), e->stream));
     }
+    return GOL_OK;
+}
+
+gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner) return gol_activity_probed(e->inner, probed_units);
+    uint64_t c = 0;
+    if (!e->parts.empty()) {
+        for (auto* p : e->parts) {
+            uint64_t pc = 0;
+            gol_status st = gol_activity_probed(p, &pc);
+            if (st != GOL_OK) return st;
+            c += pc;
+        }
+    } else if (e->d_streak) {
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        std::vector<uint32_t> v((size_t)e->act_units);
+        HIP_TRY(hipMemcpy(v.data(), e->d_streak + 5 * e->act_units + 2,
+                          v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t x : v) c += x;
+    }
+    if (probed_units) *probed_units = c;
     return GOL_OK;
 }
 

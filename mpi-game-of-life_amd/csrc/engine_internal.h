@@ -330,6 +330,10 @@ struct gol_engine {
     // launches too (GOL_DEV_COPY_THROUGH, default 2); still_on: the one-load exit
     // (GOL_DEV_STILL_EXIT=0 turns it off).  act_hist: the streak parity the step's
     // last depth-K launch wrote, -1 while the step has no history.
+    // Last, act_units "probed" counters: units that a step's first launch found
+    // still after one generation (the still probe; probe_on,
+    // GOL_DEV_STILL_PROBE=0 turns it off).
+    bool probe_on = false;
     uint32_t* d_streak = nullptr;
     int64_t act_units = 0;
     bool act_on = false;

@@ -128,6 +128,10 @@ struct StepArgs {
     // launch_idx + 1 (the launch's index within its step) to busy[1]; a launch
     // that finds busy[1] < launch_idx skips as a whole, and its unit 0 counts it in
     // busy[0].
+    // Still probe (`probe`, set with no_hist): a unit of a launch without history
+    // runs one generation over its stream first and, where that equals the input
+    // on its rectangles dilated by depth - 1, stores its input rows and ends quiet;
+    // it counts in act as computed and in probed[unit], not in copied.
     const uint32_t* streak_in;
     uint32_t* streak_out;
     const uint32_t* nb_off;
@@ -135,7 +139,9 @@ struct StepArgs {
     uint32_t* act;
     uint32_t* copied;
     uint32_t* busy;
+    uint32_t* probed;
     int32_t no_hist;
+    int32_t probe;
     int32_t through;
     int32_t launch_idx;
 };

@@ -167,6 +167,7 @@ constexpr uint32_t kFour = 0x42;      // ~(a ^ b) & (a ^ c)
 constexpr uint32_t kAndNot = 0x40;    // a & b & ~c
 constexpr uint32_t kOrAnd2 = 0xEA;    // (a & b) | c
 constexpr uint32_t kOrXor = 0xF6;     // a | (b ^ c)
+constexpr uint32_t kXorAnd = 0x28;    // (a ^ b) & c
 
 // Horizontal neighbours of a lane group x (bitlayout.h).  Plane k's left
 // neighbours are plane k-1 and its right neighbours plane k+1, at the same bit,
@@ -805,17 +806,30 @@ void life_tb_kernel(StepArgs a)
     uint64_t wl_pi = 0, wl_pl = 0;
 #endif
     if constexpr (kTrack) {
+        // Rows [rb, re) of the unit as copy-through and the still probe move them
+        // from pbuf[0] to pbuf[1]: exactly the rows and lanes `store` would store, in
+        // the unit's output lanes (lanes 32-63 of a pair unit: their own row block,
+        // row_off in voff), read as `ingest` reads them (`ok`: the row is inside the
+        // buffer and the field).
+        const char* src = reinterpret_cast<const char*>(a.pbuf[0] + (sg.base_row + rb) * a.stride) + voff;
+        char* dst = reinterpret_cast<char*>(a.pbuf[1] + (sg.base_row + rb) * a.stride) + voff;
+        const int32_t n = (int32_t)(re - rb);
+        const int32_t c_lo = (int32_t)(vlo - rb), c_hi = (int32_t)(vhi - rb);
+        auto row_in = [&](const Grp<NP>& g, bool ok) -> Pl<NP> {
+            Pl<NP> x = planes_of(g);
+#pragma unroll
+            for (int k = 0; k < NP; ++k) x.v[k] = ok ? (x.v[k] & cm.v[k]) : 0u;
+            return x;
+        };
+        auto put_row = [&](int32_t r, const Pl<NP>& x) {  // r: rows from rb
+            if (r >= 0 && r < n && st_lane)
+                *reinterpret_cast<Grp<NP>*>(dst + (int64_t)r * row_bytes) = words_of(x);
+        };
         if (through) {
-            // Copy-through (see the prologue): exactly the rows and lanes `store`
-            // would store, rows [rb, re) in the unit's output lanes (lanes 32-63 of a
-            // pair unit: their own row block, row_off in voff), read as `ingest`
-            // reads them.  kCopyRows row loads are in flight before the first store;
-            // the last chunk loads its rows again from the block's last row on.
+            // Copy-through (see the prologue).  kCopyRows row loads are in flight
+            // before the first store; the last chunk loads its rows again from the
+            // block's last row on.
             constexpr int kCopyRows = 16;
-            const char* src = reinterpret_cast<const char*>(a.pbuf[0] + (sg.base_row + rb) * a.stride) + voff;
-            char* dst = reinterpret_cast<char*>(a.pbuf[1] + (sg.base_row + rb) * a.stride) + voff;
-            const int32_t n = (int32_t)(re - rb);
-            const int32_t c_lo = (int32_t)(vlo - rb), c_hi = (int32_t)(vhi - rb);
             auto load_rows = [&](Grp<NP> (&g)[kCopyRows], int32_t r0) {
 #pragma unroll
                 for (int j = 0; j < kCopyRows; ++j) {
@@ -827,13 +841,7 @@ void life_tb_kernel(StepArgs a)
 #pragma unroll
                 for (int j = 0; j < kCopyRows; ++j) {
                     const int32_t r = r0 + j;
-                    if (r < n && st_lane) {
-                        const bool ok = r >= c_lo && r < c_hi;
-                        Pl<NP> x = planes_of(g[j]);
-#pragma unroll
-                        for (int k = 0; k < NP; ++k) x.v[k] = ok ? (x.v[k] & cm.v[k]) : 0u;
-                        *reinterpret_cast<Grp<NP>*>(dst + (int64_t)r * row_bytes) = words_of(x);
-                    }
+                    put_row(r, row_in(g[j], r >= c_lo && r < c_hi));
                 }
             };
             // (two chunks in turn, the next one's loads issued before this one's
@@ -850,6 +858,100 @@ void life_tb_kernel(StepArgs a)
                 if (a.copied) a.copied[unit] += 1u;
             }
             return;
+        }
+        // Still probe (StepArgs::probe; the first launch of a step, which has no
+        // history).  One generation over the unit's whole stream, rows
+        // [rb - K, re + K) in all 64 lanes, through one stage: generation 1 is exact
+        // on the rows [rb - K + 1, re + K - 1) and on every column the wavefront
+        // holds but the outermost one of a lane whose outer neighbour the lane shift
+        // does not supply.  Compared are those rows in the columns `keep`: the unit's
+        // output rectangles dilated by K - 1 cells.  Where generation 1 equals the
+        // input on that set, generation k equals the input on it shrunk by k - 1, so
+        // the unit's output rows are its input rows and it ends the launch quiet.
+        // The input rows of [rb, re) are stored as they pass; the first chunk with a
+        // difference leaves for the compute path below, which stores every row again.
+        if (a.probe && a.streak_out && a.no_hist && n > 0) {
+            // rows per chunk (even: a chunk starts at an even step).  4 where 16
+            // would cost the kernel registers it does not otherwise need: the
+            // shallow kernels, which serve as remainder launches without a probe,
+            // and the generic rule's long mask sum
+            constexpr int kProbeRows = (K >= 8 && RULE != RULE_GENERIC) ? 16 : 4;
+            const char* in0 = src - (int64_t)K * row_bytes;  // the row of step 0
+            const int32_t p_lo = c_lo + K, p_hi = c_hi + K;  // steps inside buffer and field
+            // (births) steps whose row is a field row, as row_mask below
+            const int32_t pf_lo = (int32_t)(-(sg.glob0 + rb - K));
+            const int32_t pf_hi = (int32_t)(sg.field_h - (sg.glob0 + rb - K));
+            // `keep`: every column of a lane that stores; of the lane beside the
+            // strip's first or last storing lane, the K - 1 columns next to it
+            // (column c of a group is bit c / NP of plane c % NP), which never
+            // reach that lane's far column
+            static_assert(K - 1 < 32 * NP, "the dilation stays inside the neighbour lane");
+            const bool st_l = lane_from_left(st_lane ? 1u : 0u) != 0u;   // lane - 1 stores
+            const bool st_r = lane_from_right(st_lane ? 1u : 0u) != 0u;  // lane + 1 stores
+            Pl<NP> keep;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                constexpr int m = K - 1;
+                // bits of plane k among the group's first m columns / before its last m
+                const int first = m > k ? (m - k + NP - 1) / NP : 0;
+                const int below = 32 * NP - m > k ? (32 * NP - m - k + NP - 1) / NP : 0;
+                const uint32_t lo = (uint32_t)((1ull << first) - 1ull);
+                const uint32_t hi = ~(uint32_t)((1ull << below) - 1ull);
+                keep.v[k] = st_lane ? ~0u : ((st_l ? lo : 0u) | (st_r ? hi : 0u));
+            }
+            auto load_probe = [&](int32_t t) -> Grp<NP> {
+                return load_field<NP>(reinterpret_cast<const uint64_t*>(
+                    in0 + (int64_t)min(t, T - 1) * row_bytes));
+            };
+            StageT<NP> pst = {};
+            Pl<NP> moved = {};  // OR of (generation 1) ^ (input) over the exact rows
+            Grp<NP> g[kProbeRows];
+#pragma unroll
+            for (int j = 0; j < kProbeRows; ++j) g[j] = load_probe(j);
+            bool quiet = true;
+            for (int32_t t0 = 0; t0 < T; t0 += kProbeRows) {
+                Pl<NP> x[kProbeRows];
+#pragma unroll
+                for (int j = 0; j < kProbeRows; ++j) {
+                    x[j] = row_in(g[j], t0 + j >= p_lo && t0 + j < p_hi);
+                    g[j] = load_probe(t0 + kProbeRows + j);
+                }
+#pragma unroll
+                for (int j = 0; j < kProbeRows; ++j) {
+                    const int32_t t = t0 + j;
+                    // step t ingests row t and emits generation 1 of row t - 1, which
+                    // the stage holds as `al`; exact for t in [2, T)
+                    const Pl<NP> was = pst.al;
+                    Pl<NP> y = stage_step<RULE>(pst, x[j], a.birth, a.survive, (j & 1) == 0);
+                    if constexpr (kBirths) {
+                        const uint32_t rm = __builtin_amdgcn_readfirstlane(
+                            (t - 1 >= pf_lo && t - 1 < pf_hi) ? ~0u : 0u);
+#pragma unroll
+                        for (int k = 0; k < NP; ++k) y.v[k] = lop3<kAnd3>(y.v[k], cm.v[k], rm);
+                    }
+                    const uint32_t in_dom =
+                        __builtin_amdgcn_readfirstlane((t >= 2 && t < T) ? ~0u : 0u);
+#pragma unroll
+                    for (int k = 0; k < NP; ++k)
+                        moved.v[k] |= lop3<kXorAnd>(y.v[k], was.v[k], in_dom);
+                    put_row(t - K, x[j]);
+                }
+                uint32_t d = 0;
+#pragma unroll
+                for (int k = 0; k < NP; ++k) d |= moved.v[k] & keep.v[k];
+                if (__builtin_amdgcn_ballot_w64(d != 0u) != 0) {
+                    quiet = false;
+                    break;
+                }
+            }
+            if (quiet) {
+                if (lane == 0) {
+                    a.streak_out[unit] = min(streak + 1u, kStreakCap);
+                    if (a.act) a.act[2 * unit] += 1u;
+                    if (a.probed) a.probed[unit] += 1u;
+                }
+                return;
+            }
         }
     }
     for (int pass = 0; pass < npass; ++pass) {

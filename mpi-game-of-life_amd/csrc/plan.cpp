@@ -849,8 +849,9 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
     if (e->nranks <= 1 && max_units > 0) {
         // activity skip: the streak words of both launch parities, then the
         // computed / skipped counters (2 per unit), the copied counters (1 per
-        // unit) and the two words of the one-load exit
-        const size_t words = 5 * (size_t)max_units + 2;
+        // unit), the two words of the one-load exit and the probed counters (1
+        // per unit)
+        const size_t words = 6 * (size_t)max_units + 2;
         HIP_TRY(hipMalloc(&e->d_streak, words * sizeof(uint32_t)));
         HIP_TRY(hipMemset(e->d_streak, 0, words * sizeof(uint32_t)));
         e->act_units = max_units;

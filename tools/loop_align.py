@@ -79,6 +79,27 @@ def vgpr_counts(notes):
     return out
 
 
+def is_probe_loop(text):
+    """(r09) The still probe's loop holds stage logic too, but one stage-step per
+    loaded row (two v_alignbit each) whatever the kernel's depth, and the vector
+    compare of the ballot that ends each chunk; a steady loop has K stage-steps per
+    row and compares on the scalar unit only."""
+    mn = [l.split()[0] for l in text if l.split()]
+    align = sum(m.startswith("v_alignbit") for m in mn)
+    loads = sum(m.startswith("global_load") for m in mn)
+    return align == 2 * loads and any(m.startswith("v_cmp") for m in mn)
+
+
+def drop_probe_loops(loops, text_of):
+    """`loops` ((lo, hi) pairs) without the probe loops and without the backward
+    branches the block layout wraps around one: ranges that hold a probe loop and
+    no stage logic beyond it."""
+    n_align = lambda r: sum("v_alignbit" in l for l in text_of(r))
+    probes = [r for r in loops if is_probe_loop(text_of(r))]
+    return [r for r in loops if r not in probes and
+            not any(r[0] <= p[0] and p[1] <= r[1] and n_align(r) == n_align(p) for p in probes)]
+
+
 def main_loop_fractions(body, births):
     """[(mask, fraction of the loop's 8-byte instructions at 4 mod 8, count)] for the
     steady-state loops: one for B/S2 kernels; for kernels with births (r04) the
@@ -97,10 +118,11 @@ def main_loop_fractions(body, births):
         if m and int(m.group(1), 16) + base < a:
             loops.append((int(m.group(1), 16) + base, a))
     cands = []
-    for lo, hi in loops:
+    text_of = lambda r: [l for a, _, l in ins if r[0] <= a <= r[1]]
+    for lo, hi in drop_probe_loops(loops, text_of):
         eight = [a for a, sz, _ in ins if lo <= a <= hi and sz == 8]
         # (r08: the copy-through loop has 8-byte loads and stores and no stage logic)
-        if len(eight) >= 32 and any("v_alignbit" in l for a, _, l in ins if lo <= a <= hi):
+        if len(eight) >= 32 and any("v_alignbit" in l for l in text_of((lo, hi))):
             cands.append((lo, hi, eight))
     if not cands:
         return []

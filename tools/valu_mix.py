@@ -45,6 +45,8 @@ def loop_body(body):
         m = re.search(r"s_c?branch\w* .*\+0x([0-9a-f]+)>", l)
         if m and int(m.group(1), 16) + base < a:
             loops.append((int(m.group(1), 16) + base, a))
+    # (r09: not the still probe's loop, loop_align.drop_probe_loops)
+    loops = la.drop_probe_loops(loops, lambda r: [l for a, _, _, l in ins if r[0] <= a <= r[1]])
     cands = [(lo, hi, sum(1 for a, sz, _, _ in ins if lo <= a <= hi and sz == 8))
              for lo, hi in loops]
     # (r08: not the copy-through loop, 8-byte loads and stores without stage logic)
