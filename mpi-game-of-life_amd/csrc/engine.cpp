@@ -14,11 +14,8 @@ namespace golh __attribute__((visibility("hidden"))) {
 
 thread_local std::string g_last_error;
 
-#if GOL_EXP
-// Dev timing builds (tools/exp_build.sh): device buffer the stencil kernel logs
-// per-wavefront (start, end, hardware id, unit) into; set by gol_dev_set_wave_log.
+#if GOL_WAVE_LOG
 uint64_t* g_dev_wave_log = nullptr;
-uint32_t* g_dev_prog = nullptr;  // GOL_EXP & 1024: per-SIMD progress words
 #endif
 
 }  // namespace golh
@@ -527,7 +524,7 @@ gol_status step_resident(gol_engine* e, uint64_t generations)
         a.flag_base = r.flag_base;
         a.birth = e->birth;
         a.survive = e->survive;
-#if GOL_EXP
+#if GOL_WAVE_LOG
         a.wlog = g_dev_wave_log;
 #endif
         hipEvent_t e0, e1;
@@ -567,11 +564,6 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     StepArgs a{};
     for (int i = 0; i <= passes; ++i) a.pbuf[i] = e->buf[(e->cur + i) % e->nbuf];
     a.npass = passes;
-#if GOL_EXP
-    // (timing-only switches that invalidate the field: experimental builds only)
-    if (passes > 1)
-        if (const char* v = std::getenv("GOL_DEV_MP_FLAGS")) a.mp_dev = (uint32_t)std::atoi(v);
-#endif
     a.shadow_off = e->shadow_off;
     a.mpflags = e->mpflags;
     a.err = e->d_err;
@@ -632,26 +624,27 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     // last depth-K launch wrote, and only to copy still units through (its depths
     // add up to less than K, so the lists, dilated by K, cover every one of them).
     if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
-        a.act = e->d_streak + 2 * e->act_units;
-        a.copied = e->d_streak + 4 * e->act_units;
+        const ActState st{e->d_streak, (size_t)e->act_units};
+        a.act = st.act();
+        a.copied = st.copied();
         const bool may = e->act_on && !e->timing_every && !hand && passes == 1 && p.d_nb &&
                          p.npass == 1 && e->nbuf == 2 && !a.xcd_shift &&
                          p.total_units <= e->act_units;
         if (may && depth == e->K) {
             const int par = e->act_launch & 1;
-            a.streak_in = e->d_streak + (size_t)par * e->act_units;
-            a.streak_out = e->d_streak + (size_t)(par ^ 1) * e->act_units;
+            a.streak_in = st.streak(par);
+            a.streak_out = st.streak(par ^ 1);
             a.nb_off = p.d_nb;
             a.nb_ids = p.d_nb + p.nb_off.size();
             a.no_hist = e->act_launch == 0 ? 1 : 0;
             a.probe = (a.no_hist && e->probe_on) ? 1 : 0;
-            a.probed = e->d_streak + 5 * e->act_units + 2;
+            a.probed = st.probed();
             a.through = e->through_on >= 1 ? 1 : 0;
-            a.busy = e->still_on ? e->d_streak + 5 * e->act_units : nullptr;
+            a.busy = e->still_on ? st.busy() : nullptr;
             a.launch_idx = e->act_launch;
             e->act_hist = par ^ 1;
         } else if (may && depth < e->K && e->act_hist >= 0 && e->through_on >= 2) {
-            a.streak_in = e->d_streak + (size_t)e->act_hist * e->act_units;
+            a.streak_in = st.streak(e->act_hist);
             a.nb_off = p.d_nb;
             a.nb_ids = p.d_nb + p.nb_off.size();
             a.through = 1;
@@ -660,9 +653,8 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         }
         ++e->act_launch;
     }
-#if GOL_EXP
+#if GOL_WAVE_LOG
     a.wlog = g_dev_wave_log;
-    a.prog = g_dev_prog;
 #endif
     hipEvent_t e0, e1;
     GOL_TRY(timing_begin(e, s, &e0, &e1));
@@ -1633,6 +1625,45 @@ static gol_status rect_bounds(const gol_engine* e, uint64_t y, uint64_t x, uint6
                                 std::to_string(e->W) + (e->inner ? " torus" : " field"));
 }
 
+// The activity counters of an engine, summed over its units (and over the parts
+// of a composite engine), after everything issued on its stream has run.
+struct ActTotals {
+    uint64_t computed = 0, skipped = 0, copied = 0, probed = 0;
+};
+static gol_status read_activity(gol_engine* e, ActTotals& t)
+{
+    if (e->inner) return read_activity(e->inner, t);
+    for (auto* part : e->parts) GOL_TRY(read_activity(part, t));
+    if (!e->parts.empty() || !e->d_streak) return GOL_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const ActState dev{e->d_streak, (size_t)e->act_units};
+    std::vector<uint32_t> host(dev.words());
+    HIP_TRY(hipMemcpy(host.data(), dev.base, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const ActState st{host.data(), dev.units};
+    for (size_t u = 0; u < st.units; ++u) {
+        t.computed += st.act()[2 * u];
+        t.skipped += st.act()[2 * u + 1];
+        t.copied += st.copied()[u];
+        t.probed += st.probed()[u];
+    }
+    // launches that every unit skipped at the one-load exit (only plan 0's
+    // launches of a step ever skip)
+    if (!e->plans.empty()) t.skipped += (uint64_t)st.busy()[0] * (uint64_t)e->plans[0].total_units;
+    return GOL_OK;
+}
+
+// The plan that the gol_plan_* getters and gol_info describe, and in `e` the
+// engine that owns it: the inner engine of a torus, the first part of a composite
+// engine; of a rank engine plans[Hx - 1], the full-round launch over its own rows
+// (the band and interior plans come after it), else plans[0].  Null: no plan.
+static const gol_engine::Plan* described_plan(gol_engine*& e)
+{
+    while (e->inner || !e->parts.empty()) e = e->inner ? e->inner : e->parts[0];
+    if (e->plans.empty()) return nullptr;
+    return e->nranks > 1 ? &e->plans[e->Hx - 1] : &e->plans[0];
+}
+
 }  // namespace golh
 
 extern "C" {
@@ -1812,13 +1843,14 @@ gol_status gol_reset_timing(gol_engine* e)
     e->tm = gol_timing{};
     if (e->d_streak) {
         HIP_TRY(hipSetDevice(e->device));
-        // the computed / skipped and copied counters and the count of launches
-        // skipped as a whole
-        HIP_TRY(hipMemsetAsync(e->d_streak + 2 * e->act_units, 0,
-                               (3 * (size_t)e->act_units + 1) * sizeof(uint32_t), e->stream));
-        // the probed counters, behind the two words of the one-load exit
-        HIP_TRY(hipMemsetAsync(e->d_streak + 5 * e->act_units + 2, 0,
-                               (size_t)e->act_units * sizeof(uint32_t), e->stream));
+        // Every counter: computed / skipped, copied and busy[0] lie one after the
+        // other, the probed ones behind busy[1].  The streaks and busy[1] are not
+        // statistics but the skip's own state within a step, which each step's
+        // first launch starts afresh: a reset leaves them alone.
+        const ActState as{e->d_streak, (size_t)e->act_units};
+        HIP_TRY(hipMemsetAsync(as.act(), 0, (size_t)(as.busy() + 1 - as.act()) * sizeof(uint32_t),
+                               e->stream));
+        HIP_TRY(hipMemsetAsync(as.probed(), 0, as.units * sizeof(uint32_t), e->stream));
     }
     return GOL_OK;
 }
@@ -1826,83 +1858,28 @@ gol_status gol_reset_timing(gol_engine* e)
 gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
-    if (e->inner) return gol_activity_probed(e->inner, probed_units);
-    uint64_t c = 0;
-    if (!e->parts.empty()) {
-        for (auto* p : e->parts) {
-            uint64_t pc = 0;
-            gol_status st = gol_activity_probed(p, &pc);
-            if (st != GOL_OK) return st;
-            c += pc;
-        }
-    } else if (e->d_streak) {
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        std::vector<uint32_t> v((size_t)e->act_units);
-        HIP_TRY(hipMemcpy(v.data(), e->d_streak + 5 * e->act_units + 2,
-                          v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (uint32_t x : v) c += x;
-    }
-    if (probed_units) *probed_units = c;
+    ActTotals t;
+    GOL_TRY(read_activity(e, t));
+    if (probed_units) *probed_units = t.probed;
     return GOL_OK;
 }
 
 gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
-    if (e->inner) return gol_activity_copied(e->inner, copied_units);
-    uint64_t c = 0;
-    if (!e->parts.empty()) {
-        for (auto* p : e->parts) {
-            uint64_t pc = 0;
-            gol_status st = gol_activity_copied(p, &pc);
-            if (st != GOL_OK) return st;
-            c += pc;
-        }
-    } else if (e->d_streak) {
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        std::vector<uint32_t> v((size_t)e->act_units);
-        HIP_TRY(hipMemcpy(v.data(), e->d_streak + 4 * e->act_units, v.size() * sizeof(uint32_t),
-                          hipMemcpyDeviceToHost));
-        for (uint32_t x : v) c += x;
-    }
-    if (copied_units) *copied_units = c;
+    ActTotals t;
+    GOL_TRY(read_activity(e, t));
+    if (copied_units) *copied_units = t.copied;
     return GOL_OK;
 }
 
 gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
-    if (e->inner) return gol_activity(e->inner, computed_units, skipped_units);
-    uint64_t c = 0, k = 0;
-    if (!e->parts.empty()) {
-        for (auto* p : e->parts) {
-            uint64_t pc = 0, pk = 0;
-            gol_status st = gol_activity(p, &pc, &pk);
-            if (st != GOL_OK) return st;
-            c += pc;
-            k += pk;
-        }
-    } else if (e->d_streak) {
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        std::vector<uint32_t> v(2 * (size_t)e->act_units);
-        HIP_TRY(hipMemcpy(v.data(), e->d_streak + 2 * e->act_units, v.size() * sizeof(uint32_t),
-                          hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < v.size(); i += 2) {
-            c += v[i];
-            k += v[i + 1];
-        }
-        // launches that every unit skipped at the one-load exit (only plan 0's
-        // launches of a step ever skip)
-        uint32_t still = 0;
-        HIP_TRY(hipMemcpy(&still, e->d_streak + 5 * e->act_units, sizeof(uint32_t),
-                          hipMemcpyDeviceToHost));
-        if (!e->plans.empty()) k += (uint64_t)still * (uint64_t)e->plans[0].total_units;
-    }
-    if (computed_units) *computed_units = c;
-    if (skipped_units) *skipped_units = k;
+    ActTotals t;
+    GOL_TRY(read_activity(e, t));
+    if (computed_units) *computed_units = t.computed;
+    if (skipped_units) *skipped_units = t.skipped;
     return GOL_OK;
 }
 
@@ -1930,13 +1907,11 @@ gol_status gol_info(gol_engine* e, uint64_t* h, uint64_t* w, uint64_t* row0, uin
         if (rows) *rows = e->H;
         return GOL_OK;
     }
-    // (rank engines: plans[Hx-1], the round's full-depth launch; the band and
-    // interior plans come after it)
-    const size_t full = (e->nranks > 1 && e->Hx >= 1 && e->plans.size() >= e->Hx) ? e->Hx - 1
-                                                                                   : e->plans.size() - 1;
-    if (rows_per_wave)
-        *rows_per_wave = e->res.on ? (uint32_t)e->res.rows
-                                   : e->plans.empty() ? 0 : (uint32_t)e->plans[full].rpw;
+    // (a rank engine that holds fewer than its Hx round plans: the last it has)
+    const bool last =
+        e->nranks > 1 && !(e->Hx >= 1 && e->plans.size() >= e->Hx) && !e->plans.empty();
+    const gol_engine::Plan* p = last ? &e->plans.back() : described_plan(e);
+    if (rows_per_wave) *rows_per_wave = e->res.on ? (uint32_t)e->res.rows : p ? (uint32_t)p->rpw : 0;
     if (h) *h = e->H;
     if (w) *w = e->W;
     if (row0) *row0 = e->row0;
@@ -1950,13 +1925,10 @@ gol_status gol_plan_info(gol_engine* e, uint32_t* strip_lanes, uint32_t* rows_pe
                          uint32_t* word_planes)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
-    if (e->inner) return gol_plan_info(e->inner, strip_lanes, rows_per_wave, word_planes);
-    if (!e->parts.empty())
-        return gol_plan_info(e->parts[0], strip_lanes, rows_per_wave, word_planes);
+    const gol_engine::Plan* pp = described_plan(e);
     if (word_planes) *word_planes = (uint32_t)e->planes;
-    if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
-    // rank engines: plans[Hx-1] is the full-round launch over own rows; else plans[0]
-    const auto& p = e->nranks > 1 ? e->plans[e->Hx - 1] : e->plans[0];
+    if (!pp) return fail(GOL_ESTATE, "no launch plan");
+    const auto& p = *pp;
     if (strip_lanes) *strip_lanes = e->res.on ? 64u : (uint32_t)(64 >> p.lane_shift);
     if (rows_per_wave) *rows_per_wave = e->res.on ? (uint32_t)e->res.rows : (uint32_t)p.rpw;
     return GOL_OK;
@@ -1966,10 +1938,9 @@ gol_status gol_plan_skew(gol_engine* e, uint32_t* rows_old, uint32_t* rows_young
                          uint32_t* units_old)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
-    if (e->inner) return gol_plan_skew(e->inner, rows_old, rows_young, units_old);
-    if (!e->parts.empty()) return gol_plan_skew(e->parts[0], rows_old, rows_young, units_old);
-    if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
-    const auto& p = e->nranks > 1 ? e->plans[e->Hx - 1] : e->plans[0];
+    const gol_engine::Plan* pp = described_plan(e);
+    if (!pp) return fail(GOL_ESTATE, "no launch plan");
+    const auto& p = *pp;
     const bool on = !e->res.on && p.rows_old;
     if (rows_old) *rows_old = on ? (uint32_t)p.rows_old : 0u;
     if (rows_young) *rows_young = on ? (uint32_t)p.rows_young : 0u;
@@ -1980,10 +1951,9 @@ gol_status gol_plan_columns(gol_engine* e, uint32_t* strips, uint32_t* half_unit
                             uint32_t* half_groups)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
-    if (e->inner) return gol_plan_columns(e->inner, strips, half_units, half_groups);
-    if (!e->parts.empty()) return gol_plan_columns(e->parts[0], strips, half_units, half_groups);
-    if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
-    const auto& p = e->nranks > 1 ? e->plans[e->Hx - 1] : e->plans[0];
+    const gol_engine::Plan* pp = described_plan(e);
+    if (!pp) return fail(GOL_ESTATE, "no launch plan");
+    const auto& p = *pp;
     const bool on = !e->res.on;
     if (strips) *strips = on ? (uint32_t)p.groups : (uint32_t)e->res.strips;
     if (half_units) *half_units = on ? (uint32_t)p.pair_units : 0u;
@@ -2024,10 +1994,9 @@ gol_status gol_plan_resident_rows(gol_engine* e, uint32_t* rows, uint32_t* band_
 gol_status gol_plan_handoff(gol_engine* e, uint32_t* handoff)
 {
     if (!e || !handoff) return fail(GOL_EINVAL, "null argument");
-    if (e->inner) return gol_plan_handoff(e->inner, handoff);
-    if (!e->parts.empty()) return gol_plan_handoff(e->parts[0], handoff);
-    if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
-    const auto& p = e->nranks > 1 ? e->plans[e->Hx - 1] : e->plans[0];
+    const gol_engine::Plan* pp = described_plan(e);
+    if (!pp) return fail(GOL_ESTATE, "no launch plan");
+    const auto& p = *pp;
     *handoff = (!e->res.on && p.hand && p.multi_blk && e->side[0] && handoff_fits(p.rpw, (int)e->K, e->planes))
                    ? 1u
                    : 0u;
@@ -2036,10 +2005,9 @@ gol_status gol_plan_handoff(gol_engine* e, uint32_t* handoff)
 
 }  // extern "C"
 
-#if GOL_EXP
-// Dev timing builds only: log every stencil wavefront's (start, end) s_memrealtime
-// stamps, HW_ID | XCC_ID << 32 and unit into `dev` (4 words per wavefront; null
-// turns the log off).  Not part of include/gol.h.
+#if GOL_WAVE_LOG
+// GOL_WAVE_LOG builds only: the kernels log 8 words per wavefront into `dev`
+// (StepArgs::wlog, ResArgs::wlog; null turns the log off).  Not part of include/gol.h.
 extern "C" __attribute__((visibility("default"))) void gol_dev_set_wave_log(void* dev)
 {
     g_dev_wave_log = static_cast<uint64_t*>(dev);

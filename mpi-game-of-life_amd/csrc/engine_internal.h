@@ -41,12 +41,31 @@ using gol::StepArgs;
 
 extern thread_local std::string g_last_error;
 
-#if GOL_EXP
-// Dev timing builds (tools/exp_build.sh): device buffer the stencil kernel logs
-// per-wavefront (start, end, hardware id, unit) into; set by gol_dev_set_wave_log.
+#if GOL_WAVE_LOG
+// device buffer the kernels log per-wavefront stamps into (life_internal.h); set by
+// gol_dev_set_wave_log
 extern uint64_t* g_dev_wave_log;
-extern uint32_t* g_dev_prog;  // GOL_EXP & 1024: per-SIMD progress words
 #endif
+
+// The activity state (gol_engine::d_streak; StepArgs in life_internal.h says how
+// the kernel uses each region): words of a buffer of `units` units, on the device
+// or a host copy of it.
+struct ActState {
+    uint32_t* base;
+    size_t units;
+    // per unit: quiet launches so far, as the launches of one parity wrote them
+    uint32_t* streak(int parity) const { return base + (size_t)parity * units; }
+    // per unit: launches computed, launches skipped
+    uint32_t* act() const { return base + 2 * units; }
+    // per unit: launches copied through
+    uint32_t* copied() const { return base + 4 * units; }
+    // [0] launches that skipped as a whole, [1] index + 1 of the step's last launch
+    // in which a unit stored rows
+    uint32_t* busy() const { return base + 5 * units; }
+    // per unit: first launches of a step that found it still after one generation
+    uint32_t* probed() const { return base + 5 * units + 2; }
+    size_t words() const { return 6 * units + 2; }
+};
 
 // gol_create splits GLOBAL fields of at least this many rows into 2 same-device
 // stripes on 2 streams (measured +11% at 65536^2; no gain at <= 16384 rows,
@@ -318,29 +337,23 @@ struct gol_engine {
     uint32_t* flags[2] = {nullptr, nullptr};
     int* d_err = nullptr;
 
-    // Activity skip (life_stencil.h).  d_streak: 2 x act_units streak
-    // words (by launch parity), then 2 x act_units counters (computed, skipped per
-    // unit).  act_on: the engine may skip (decided at create).  act_launch: index of
-    // the next stencil launch within the gol_step that is being issued, -1 outside
-    // one: history never outlives a step, so nothing that touches the field
-    // between steps can leave a stale streak.
-    // Then act_units "copied" counters and two words: the launches skipped as a
-    // whole and the index + 1 of the last launch in which a unit stored rows.
-    // through_on: 0 = no copy-through, 1 = launches at depth K, 2 = the remainder
-    // launches too (GOL_DEV_COPY_THROUGH, default 2); still_on: the one-load exit
-    // (GOL_DEV_STILL_EXIT=0 turns it off).  act_hist: the streak parity the step's
-    // last depth-K launch wrote, -1 while the step has no history.
-    // Last, act_units "probed" counters: units that a step's first launch found
-    // still after one generation (the still probe; probe_on,
-    // GOL_DEV_STILL_PROBE=0 turns it off).
-    bool probe_on = false;
+    // Activity skip (life_stencil.h).  d_streak: the device state of
+    // act_units units, laid out as ActState says (single-GPU engines with a plan).
+    // act_launch: index of the next stencil launch within the gol_step that is
+    // being issued, -1 outside one: history never outlives a step, so nothing that
+    // touches the field between steps can leave a stale streak.  act_hist: the
+    // streak parity the step's last depth-K launch wrote, -1 while the step has no
+    // history.
     uint32_t* d_streak = nullptr;
     int64_t act_units = 0;
-    bool act_on = false;
     int act_launch = -1;
-    int through_on = 0;
-    bool still_on = false;
     int act_hist = -1;
+    // what the engine may do, decided at create:
+    bool act_on = false;    // skip units at all
+    int through_on = 0;     // copy-through: 0 = off, 1 = launches at depth K, 2 = the
+                            // remainder launches too (GOL_DEV_COPY_THROUGH, default 2)
+    bool still_on = false;  // the one-load exit (GOL_DEV_STILL_EXIT=0 turns it off)
+    bool probe_on = false;  // the still probe (GOL_DEV_STILL_PROBE=0 turns it off)
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on

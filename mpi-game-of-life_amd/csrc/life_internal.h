@@ -8,6 +8,13 @@
 #ifndef GOL_DEV_KERNELS
 #define GOL_DEV_KERNELS 0
 #endif
+// Dev timing build only (tools/variant_build.sh wavelog "-DGOL_WAVE_LOG=1"): every
+// wavefront of the stencil and resident kernels logs its start/end stamps and its
+// hardware id (the stencil kernel its phase stamps too) into the buffer given to
+// gol_dev_set_wave_log (tools/wave_log.py, tools/res_log.py).  The field stays valid.
+#ifndef GOL_WAVE_LOG
+#define GOL_WAVE_LOG 0
+#endif
 
 namespace gol {
 
@@ -58,9 +65,6 @@ struct StepArgs {
     int32_t npass;
     uint32_t shadow_off;
     uint32_t* mpflags;
-    // dev timing switches (GOL_DEV_MP_FLAGS, GOL_EXP builds; the field is not valid): 2 = no
-    // inter-pass waits, 8 = no shadow for the halo lanes
-    uint32_t mp_dev;
     const SegDesc* segs;  // device table
     int32_t nseg;
     int32_t strips;       // strip groups per row: ceil(ceil(wq / (L-2)) / (64/L))
@@ -84,8 +88,7 @@ struct StepArgs {
     uint32_t* flags;      // total_units words (per pass parity), all 0 between launches
     int* err;
     int64_t side_slot;    // words per slot: 2 (K-1) rows x 64 lanes x NP/2 words
-    uint64_t* wlog;       // dev timing builds only (GOL_EXP & 128): 8 words per wavefront
-    uint32_t* prog;       // dev (GOL_EXP & 1024): per-SIMD wave progress, 2 words per SIMD
+    uint64_t* wlog;       // GOL_WAVE_LOG builds only: 8 words per wavefront
     // Edge-aligned strips and the packed half strip (plan.cpp col_layout;
     // one-segment launches of 64-lane strips).  A lane whose neighbour lane is the
     // DPP shift's zero (lane 0 / 63) or outside the field is exact, so strip 0 starts
@@ -248,7 +251,7 @@ struct ResArgs {
     int32_t gens;         // generations of this launch
     uint32_t flag_base;
     uint32_t birth, survive;
-    uint64_t* wlog;       // dev timing builds only (GOL_EXP & 2048): 4 words per wavefront
+    uint64_t* wlog;       // GOL_WAVE_LOG builds only: 8 words per wavefront, 6 used
 };
 // coop: hipLaunchCooperativeKernel, else a plain launch (engine.cpp Resident::coop)
 hipError_t launch_resident(const ResArgs& a, int rows, RuleKind rule, int grid, hipStream_t s,

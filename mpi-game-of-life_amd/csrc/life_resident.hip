@@ -234,7 +234,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
         asm volatile("" ::: "memory");
         t = *pe;
     };
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
     // dev timing build: per-wave cycles waiting for neighbour waves, in epoch
     // hand-offs, and in all (s_memtime), logged at the end
     uint64_t t_wait = 0, t_epoch = 0, t_beg = __builtin_amdgcn_s_memtime(), t_ep0 = 0;
@@ -267,18 +267,8 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
             const int p = g & 1, q = (g + 1) & 1;
             const uint4* pu = has_up ? ed4 + p * (2 * W * 64) + (W + wv - 1) * 64 + lane : zero4 + lane;
             const uint4* pd = has_dn ? ed4 + p * (2 * W * 64) + (wv + 1) * 64 + lane : zero4 + lane;
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
             const uint64_t tw0 = __builtin_amdgcn_s_memtime();
-#endif
-#if GOL_EXP & 4096
-            // dev trace (tools/res_trace.py): shader-clock stamps per generation
-            uint64_t ts[5];
-            auto stamp = [&](int j) { ts[j] = __builtin_amdgcn_s_memtime(); };
-            auto stamp_on = [&](int j, uint32_t& v) {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v));
-                ts[j] = __builtin_amdgcn_s_memtime();
-            };
-            stamp(0);
 #endif
             const uint32_t wu = word(wait_up), wd = word(wait_dn);
             asm volatile("" ::: "memory");  // edge reads issue after the progress reads
@@ -300,16 +290,13 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
             }
             __builtin_amdgcn_sched_barrier(0);
             if (__builtin_amdgcn_readfirstlane((int32_t)(wu - need)) < 0) await(wait_up, need, pu, tu);
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
             {
                 uint32_t v = tu.x;
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v));
                 t_wait += __builtin_amdgcn_s_memtime() - tw0;
                 if (v == 0x5a5a5a5au) tu.y ^= 1u;  // keeps v live (never taken on real data)
             }
-#endif
-#if GOL_EXP & 4096
-            stamp_on(1, tu.x);
 #endif
             __builtin_amdgcn_s_setprio(2);
             Pl<2> us, uc;
@@ -341,13 +328,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
                     asm volatile("" ::: "memory");  // progress word after the edge
                     set_word(my_top, need + 1u);
                 }
-#if GOL_EXP & 4096
-                stamp(2);
-#endif
                 if (__builtin_amdgcn_readfirstlane((int32_t)(wd - need)) < 0) await(wait_dn, need, pd, td);
-#if GOL_EXP & 4096
-                stamp_on(3, td.x);
-#endif
                 Pl<2> ds, dc;
                 ds.v[0] = td.x; ds.v[1] = td.y; dc.v[0] = td.z; dc.v[1] = td.w;
                 if constexpr (kPair && M > 2)
@@ -362,17 +343,6 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
                     asm volatile("" ::: "memory");
                     set_word(my_bot, need + 1u);
                 }
-#if GOL_EXP & 4096
-                stamp(4);
-                // per-generation trace of the middle tile, generations 32..95
-                const int32_t gg = done + g - 32;
-                if (a.wlog && lane == 0 && tile == G / 2 && gg >= 0 && gg < 64) {
-                    uint64_t* tl = a.wlog + 262144 + ((int64_t)wv * 64 + gg) * 8;
-#pragma unroll
-                    for (int j = 0; j < 5; ++j) tl[j] = ts[j];
-                    tl[5] = (uint64_t)(uint32_t)gmax;
-                }
-#endif
             }
             __builtin_amdgcn_s_setprio(0);
             if (publish) {
@@ -390,7 +360,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
             set_word(my_top, (uint32_t)(done + k));
             set_word(my_bot, (uint32_t)(done + k));
         }
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
         t_ep0 = __builtin_amdgcn_s_memtime();
 #endif
         done += k;
@@ -406,7 +376,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
         t_x = __builtin_amdgcn_s_memtime();
         t_pub += t_x - t_ep0;
 #endif
@@ -415,7 +385,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
             __hip_atomic_store(a.flags + tile, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (done >= a.gens) break;
         // wait for the neighbours' rows of this epoch
-        if (nb_tile >= 0 && !gave_up && !(GOL_EXP & 64)) {
+        if (nb_tile >= 0 && !gave_up) {
             uint64_t t0 = 0;
             for (int n = 0; (int32_t)(__hip_atomic_load(a.flags + nb_tile, __ATOMIC_RELAXED,
                                                         __HIP_MEMORY_SCOPE_AGENT) -
@@ -431,7 +401,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
             }
         }
         __syncthreads();
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
         t_flag += __builtin_amdgcn_s_memtime() - t_x;
 #endif
         // reload the halo rows (all lanes) and the halo lanes of the band rows
@@ -441,7 +411,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
             const bool own = r >= b0 && r < b1;
             if (!own || halo_lane) x[i] = fetch(nb, r);
         }
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
         {
             uint32_t v = x[0].v[0];
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(v));
@@ -450,7 +420,7 @@ __global__ __launch_bounds__(1024) void life_res_kernel(ResArgs a)
         }
 #endif
     }
-#if GOL_EXP & 2048
+#if GOL_WAVE_LOG
     if (a.wlog && lane == 0) {
         uint64_t* wl = a.wlog + ((int64_t)blockIdx.x * W + wv) * 8;
         wl[0] = __builtin_amdgcn_s_memtime() - t_beg;

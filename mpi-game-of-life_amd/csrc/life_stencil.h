@@ -445,16 +445,6 @@ __device__ __forceinline__ uint64_t wait_clock() { return __builtin_amdgcn_s_mem
 // Block modes of the stencil kernel (see `block`).
 constexpr int kWarmBlk = 0, kPure = 1, kSide = 2, kPureMask = 3;
 
-// Dev timing experiments only (tools/exp_build.sh; results are NOT valid): bit 0
-// skips the consumer's wait, bit 1 the producer's drain + flag, bit 2 the
-// side-row stores, bit 3 the consumer's tail; bit 7 logs every wavefront's start/end
-// stamps and hardware id (gol_dev_set_wave_log), bits 8/9 alternate s_setprio
-// between the two waves of a SIMD every steady block, bit 10 balances them closed-loop
-// (each takes priority while it is not ahead of its partner).
-#ifndef GOL_EXP
-#define GOL_EXP 0
-#endif
-// (r05) warm-up rows loaded up front (see the kernel); 0 = the r04 one-block ring
 // (r05) The warm-up's first kWarmAheadRows rows are loaded up front and each
 // warm-up block issues the rows that many steps ahead of it, with a scheduling
 // barrier between the blocks that keeps those loads where they are.  Every
@@ -465,7 +455,7 @@ constexpr int kWarmBlk = 0, kPure = 1, kSide = 2, kPureMask = 3;
 // (profiles/r05/ab_warm_ahead.jsonl), mean TCUPS of own rows, all 32 rows up
 // front / 16 / 12 / 8 ahead: 8-way 117.8 / 118.4-118.9 / 118.9 / 119.7, 4-way
 // 136.0 / 136.1-136.4 / 137.1 / 136.8; 65536^2 157.8-158.0 (16) vs 158.1-158.2
-// (8).  (The r04 one-block ring and these dev switches were removed in r06.)
+// (8).
 constexpr int kWarmAheadRows = 8;
 // the steady ring's first rows are issued this many warm-up blocks before the
 // steady loop (r05: 1 or 3 instead of 2 measured no better,
@@ -552,31 +542,8 @@ void life_tb_kernel(StepArgs a)
         }
         if (a.busy && lane == 0) a.busy[1] = (uint32_t)a.launch_idx + 1u;
     }
-#if GOL_EXP & 128
+#if GOL_WAVE_LOG
     const uint64_t wl_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#if GOL_EXP & (256 | 512)
-    // priority alternation between the two waves of a SIMD: parity from the wave
-    // slot (HW_ID.WAVE_ID, 256) or from dispatch order (first half of the grid, 512)
-    const uint32_t prio_par = (GOL_EXP & 256)
-                                  ? (__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) & 1u)
-                                  : (blockIdx.x < gridDim.x / 2 ? 0u : 1u);
-#endif
-#if GOL_EXP & 1024
-    // closed-loop balance of the two waves of a SIMD: each publishes its count of
-    // steady blocks in its SIMD's slot (HW_ID wave slot & 1) and takes priority
-    // while it is not ahead of its partner
-    uint32_t* prog_me;
-    const uint32_t* prog_mate;
-    {
-        const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
-        const uint32_t xcc = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 20) & 7;
-        const uint32_t simd = ((((xcc * 8 + ((hw >> 13) & 7)) * 2 + ((hw >> 12) & 1)) * 16 +
-                                ((hw >> 8) & 15)) * 4 + ((hw >> 4) & 3));
-        prog_me = a.prog + simd * 2 + (hw & 1);
-        prog_mate = a.prog + simd * 2 + ((hw & 1) ^ 1);
-    }
-    uint32_t prog_n = 0, prog_m = 0;
 #endif
 
     // a unit of the packed half strip (uniform): its two row blocks from the table
@@ -774,7 +741,6 @@ void life_tb_kernel(StepArgs a)
     int64_t back_unit = 0;
     // one-shot flags of the multi-pass protocol: wait until *f is set, reset it
     auto mp_wait = [&](uint32_t* f) {
-        if (a.mp_dev & 2) return;  // dev timing: no inter-pass waits (field not valid)
         uint32_t v = 0;
         uint64_t w0 = 0;
         for (int it = 0;; ++it) {
@@ -799,11 +765,8 @@ void life_tb_kernel(StepArgs a)
     auto head_flag = [&](int p, int64_t x) { return a.mpflags + (int64_t)p * a.total_units + x; };
     auto done_flag = [&](int p, int64_t x) { return a.mpflags + (int64_t)(2 + p) * a.total_units + x; };
 
-#if GOL_EXP & 128
+#if GOL_WAVE_LOG
     uint64_t wl_tb = 0, wl_tb1 = 0, wl_tw = 0, wl_ts = 0;
-#endif
-#if GOL_EXP & 16384
-    uint64_t wl_pi = 0, wl_pl = 0;
 #endif
     if constexpr (kTrack) {
         // Rows [rb, re) of the unit as copy-through and the still probe move them
@@ -987,8 +950,8 @@ void life_tb_kernel(StepArgs a)
             my_flag = a.flags + par * a.total_units + unit;
             dn_flag = a.flags + par * a.total_units + prod;
         }
-        voff_ld = voff + ((pass > 0 && halo_lane && !(a.mp_dev & 8)) ? a.shadow_off : 0u);
-        const bool wr_shadow = pass < npass - 1 && halo_lane && !(a.mp_dev & 8);
+        voff_ld = voff + ((pass > 0 && halo_lane) ? a.shadow_off : 0u);
+        const bool wr_shadow = pass < npass - 1 && halo_lane;
         voff_st = voff + (wr_shadow ? a.shadow_off : 0u);
         st_ok = st_lane || wr_shadow;
         // rows another wavefront reads in the next pass go out write-through
@@ -1035,13 +998,6 @@ void life_tb_kernel(StepArgs a)
         wring[p] = load_field<NP>(reinterpret_cast<const uint64_t*>(in_rows + (int64_t)p * rs + voff_ld));
     constexpr int kSteadyIssue =
         kWarmSteps >= kSteadyLeadBlocks * kPrefetch ? kWarmSteps - kSteadyLeadBlocks * kPrefetch : 0;
-#if GOL_EXP & 16384
-    // dev probe of a wavefront's start (tools/wave_log.py --probe): the initial
-    // loads issued, and all of them landed (results stay valid, timing does not)
-    wl_pi = __builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    wl_pl = __builtin_amdgcn_s_memrealtime();
-#endif
 
     // row of step t: an input row is dead outside the field / buffer; a side row
     // comes as the block below computed it; columns >= w masked.  SIDE: the step
@@ -1160,7 +1116,7 @@ void life_tb_kernel(StepArgs a)
         const uint32_t* f = dn_flag;
         uint32_t v = 0;
         uint64_t t0 = 0;
-        for (int it = 0; !(GOL_EXP & 1); ++it) {
+        for (int it = 0;; ++it) {
             v = __builtin_amdgcn_readfirstlane(
                 __hip_atomic_load(const_cast<uint32_t*>(f), __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_AGENT));
@@ -1170,8 +1126,7 @@ void life_tb_kernel(StepArgs a)
             __builtin_amdgcn_s_sleep(8);
         }
         if (lane == 0) {
-            if (!v && !(GOL_EXP & 1))
-                __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!v) __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // flags are all 0 between launches (and passes of one parity): reset
             // the producer's
             __hip_atomic_store(const_cast<uint32_t*>(f), 0u, __ATOMIC_RELAXED,
@@ -1182,7 +1137,7 @@ void life_tb_kernel(StepArgs a)
     auto sync_point = [&](int32_t t0) {
         const uint32_t r0 = (producer ? 1u : 0u) | (consumer ? 2u : 0u);
         const uint32_t role = MP ? opaque(r0) : r0;
-        if ((role & 1u) && t0 == kWarmSteps && !(GOL_EXP & 2)) signal();
+        if ((role & 1u) && t0 == kWarmSteps) signal();
         if ((role & 2u) && t0 + 3 * kPrefetch + TOFF > t_side && t0 + 2 * kPrefetch + TOFF <= t_side)
             wait_below();
     };
@@ -1270,7 +1225,7 @@ void life_tb_kernel(StepArgs a)
 #pragma unroll
                         for (int k = 0; k < NP; ++k) acc = lop3<kOrXor>(acc, x[p].v[k], was.v[k]);
                     }
-                    if constexpr (HAND && kGuard && !(GOL_EXP & 4)) {
+                    if constexpr (HAND && kGuard) {
                         if (g <= K - 2 && (t0 + p == 2 * g + 2 || t0 + p == 2 * g + 3))
                             store_side<NP>(reinterpret_cast<uint64_t*>(
                                                my_side + (int64_t)(t0 + p - 2) * kSideRowBytes +
@@ -1280,29 +1235,6 @@ void life_tb_kernel(StepArgs a)
                 }
             }
         }
-#if GOL_EXP & (256 | 512)
-        if constexpr (!kGuard) {
-            if (__builtin_amdgcn_readfirstlane(((uint32_t)t0 / kPrefetch ^ prio_par) & 1u))
-                __builtin_amdgcn_s_setprio(1);
-            else
-                __builtin_amdgcn_s_setprio(0);
-        }
-#endif
-#if GOL_EXP & 1024
-        if constexpr (!kGuard) {
-            // the partner's count loaded one block ago (its latency hidden by this
-            // block's compute); then publish ours and load theirs for the next block
-            if (__builtin_amdgcn_readfirstlane(prog_m) < prog_n)
-                __builtin_amdgcn_s_setprio(0);
-            else
-                __builtin_amdgcn_s_setprio(1);
-            ++prog_n;
-            if (lane == 0)
-                __hip_atomic_store(prog_me, prog_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            prog_m = __hip_atomic_load(const_cast<uint32_t*>(prog_mate), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-        }
-#endif
         if constexpr (!kGuard) {
             __builtin_amdgcn_sched_barrier(0);
             // hand-off signalling between this block's compute and its stores: the
@@ -1320,7 +1252,7 @@ void life_tb_kernel(StepArgs a)
     // Warm-up blocks, unrolled (compile-time guards).
     constexpr int kWarm = kWarmSteps;
     static_assert(!HAND || kWarm >= 2 * K, "side rows are all stored in the warm-up blocks");
-#if GOL_EXP & 128
+#if GOL_WAVE_LOG
     // (wl_tb / wl_tb1: after the first / second warm-up block)
 #pragma unroll
     for (int t0 = 0; t0 < kWarm; t0 += kPrefetch) {
@@ -1332,7 +1264,7 @@ void life_tb_kernel(StepArgs a)
 #pragma unroll
     for (int t0 = 0; t0 < kWarm; t0 += kPrefetch) block(t0, std::integral_constant<int, kWarmBlk>{});
 #endif
-#if GOL_EXP & 128
+#if GOL_WAVE_LOG
     // phase stamps (r05): issue time of the warm-up's end and the steady blocks' end
     wl_tw = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1364,12 +1296,12 @@ void life_tb_kernel(StepArgs a)
     }
     // a producer whose stream had no steady block (a short last block) signals here
     if constexpr (HAND)
-        if (producer && T <= kWarm && !(GOL_EXP & 2)) signal();
-#if GOL_EXP & 128
+        if (producer && T <= kWarm) signal();
+#if GOL_WAVE_LOG
     wl_ts = __builtin_amdgcn_s_memrealtime();
 #endif
 
-    if constexpr (HAND && !(GOL_EXP & 8)) {
+    if constexpr (HAND) {
         if (consumer) {
             // The planner keeps t_side - warm-up = TOFF (mod kPrefetch): TOFF more
             // input steps, then the ring holds the tail's first rows after a
@@ -1447,18 +1379,13 @@ void life_tb_kernel(StepArgs a)
         }
         if (a.act && lane == 0) a.act[2 * unit] += 1u;
     }
-#if GOL_EXP & 128
+#if GOL_WAVE_LOG
     if (a.wlog && lane == 0) {
         // 8 words per wavefront: start, end, HW_ID | XCC_ID, block | workgroup,
         // warm-up end, steady end (tools/wave_log.py)
         uint64_t* wl = a.wlog + unit * 8;
-#if GOL_EXP & 16384
-        wl[4] = wl_pi;
-        wl[5] = wl_pl;
-#else
         wl[4] = wl_tw;
         wl[5] = wl_ts;
-#endif
         wl[6] = (uint64_t)(re - rb) | ((wl_tb1 - wl_t0) << 32);
         wl[7] = wl_tb;
         wl[0] = wl_t0;

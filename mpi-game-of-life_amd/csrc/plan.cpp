@@ -828,12 +828,6 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
     }
     if (e->model.on) return GOL_OK;
     HIP_TRY(hipMalloc(&e->d_err, sizeof(int)));
-#if GOL_EXP
-    if (!g_dev_prog) {
-        HIP_TRY(hipMalloc(&g_dev_prog, 8192 * 2 * sizeof(uint32_t)));
-        HIP_TRY(hipMemset(g_dev_prog, 0, 8192 * 2 * sizeof(uint32_t)));
-    }
-#endif
     HIP_TRY(hipMemset(e->d_err, 0, sizeof(int)));
     if ((any_hand || any_mp) && max_units > 0) {
         // (multi-pass: hand-off slots and flags per pass parity)
@@ -847,11 +841,8 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
         }
     }
     if (e->nranks <= 1 && max_units > 0) {
-        // activity skip: the streak words of both launch parities, then the
-        // computed / skipped counters (2 per unit), the copied counters (1 per
-        // unit), the two words of the one-load exit and the probed counters (1
-        // per unit)
-        const size_t words = 6 * (size_t)max_units + 2;
+        // activity skip: streaks and counters of the largest plan's units, all 0
+        const size_t words = ActState{nullptr, (size_t)max_units}.words();
         HIP_TRY(hipMalloc(&e->d_streak, words * sizeof(uint32_t)));
         HIP_TRY(hipMemset(e->d_streak, 0, words * sizeof(uint32_t)));
         e->act_units = max_units;

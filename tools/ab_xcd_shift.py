@@ -3,7 +3,7 @@
 item 2(ii)) on THIS box, in two steps:
 
 1. the per-XCC wave timing of the 8-way rank launch shape (tools/wave_log.py on
-   the GOL_EXP & 128 build, libgol_exp128.so, in a child process): which XCCs end
+   the GOL_WAVE_LOG build, libgol_wavelog.so, in a child process): which XCCs end
    last, and whether workgroup w lands on XCC w mod 8 (the shift assumes it);
 2. the RCCL per-rank proxy (tools/rank_proxy.py, shipped library) with the shift
    off, with a table built from step 1 (the XCCs that end first take rows from
@@ -27,7 +27,7 @@ def main():
     p.add_argument("--rows", type=int, default=8416)
     p.add_argument("--rounds", type=int, default=5)
     a = p.parse_args()
-    env = dict(os.environ, GOL_LIB=os.path.join(ROOT, "mpi-game-of-life_amd", "libgol_exp128.so"))
+    env = dict(os.environ, GOL_LIB=os.path.join(ROOT, "mpi-game-of-life_amd", "libgol_wavelog.so"))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "wave_log.py"), "--rows",
                           str(a.rows), "--handoff", "2"], env=env, capture_output=True, text=True,
                          timeout=300)

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Dev tool: per-wavefront timing of the resident kernel (exp build with
-GOL_EXP & 2048, tools/exp_build.sh 2048): shader cycles in all, waiting for the
+"""Dev tool: per-wavefront timing of the resident kernel (the GOL_WAVE_LOG build,
+tools/variant_build.sh wavelog "-DGOL_WAVE_LOG=1"): shader cycles in all, waiting for the
 upper neighbour wave's edge (progress-word reads issued -> edge values in
 registers), and in the epoch hand-offs (gen loop done -> halo reload landed; of
 it: band publish + workgroup barrier, neighbour-tile flag wait + barrier).
 
-    GOL_LIB=mpi-game-of-life_amd/libgol_exp2048.so python tools/res_log.py --size 4096
+    GOL_LIB=mpi-game-of-life_amd/libgol_wavelog.so python tools/res_log.py --size 4096
 """
 import argparse
 import ctypes

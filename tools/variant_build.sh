@@ -1,8 +1,9 @@
 #!/bin/bash
-# Dev: build a variant of libgol.so with extra compile definitions (valid
-# fields, unlike tools/exp_build.sh's timing probes) as
+# Dev: build a variant of libgol.so with extra compile definitions as
 # mpi-game-of-life_amd/libgol_<NAME>.so, for in-process A/B through GOL_LIB.
 # Usage: tools/variant_build.sh NAME "-DFOO=1 -DBAR=2"
+# The per-wavefront log library of tools/wave_log.py and tools/res_log.py:
+#   tools/variant_build.sh wavelog "-DGOL_WAVE_LOG=1"
 set -e
 ROOT=$(cd $(dirname $0)/.. && pwd)
 NAME=$1; DEFS=$2

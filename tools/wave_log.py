@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Dev tool: per-wavefront timing of one stencil launch (exp builds with
-GOL_EXP & 128, tools/exp_build.sh), and the wall-clock rate of the same shape.
+"""Dev tool: per-wavefront timing of one stencil launch (the GOL_WAVE_LOG build,
+tools/variant_build.sh wavelog "-DGOL_WAVE_LOG=1"), and the wall-clock rate of the
+same shape.
 
 Each wavefront logs its s_memrealtime start/end stamps (100 MHz), HW_ID and
 XCC_ID, and (r05) the stamps where its warm-up and its steady blocks end.  Wavefronts sharing a SIMD (same XCC, SE, SH, CU, SIMD) are paired, and
@@ -8,7 +9,11 @@ the tool reports how long the first-finishing wave of a pair ends before the
 second (the time its partner runs alone on the SIMD), the spread of start and
 end stamps, and the launch span.
 
-    GOL_LIB=mpi-game-of-life_amd/libgol_exp128.so python tools/wave_log.py --rows 8448
+A unit that the still probe ends early (life_stencil.h) logs nothing, and the
+default rule's random field is still after 6 generations: log such a field with
+GOL_DEV_STILL_PROBE=0, which makes every unit of the logged launch compute.
+
+    GOL_LIB=mpi-game-of-life_amd/libgol_wavelog.so python tools/wave_log.py --rows 8448
 """
 import argparse
 import collections
@@ -33,9 +38,6 @@ def main():
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--tag", default="")
     p.add_argument("--cus", type=int, default=256)
-    p.add_argument("--probe", action="store_true",
-                   help="GOL_EXP & 16384 builds: words 4/5 are the start probe (initial loads "
-                        "issued / landed) instead of the warm-up / steady ends")
     a = p.parse_args()
     import torch
     pkg = entry.load_package()
@@ -136,12 +138,11 @@ def main():
                                           (end[i] - tsd[i]) / 100.0,
                                           (tb0[i] - start[i]) / 100.0 if tb0[i] else 0.0,
                                           (start[i] - t0) / 100.0, tb1[i] / 100.0))
-    names = ("to_loads_issued", "loads_landed", "to_end") if a.probe else ("warm", "steady", "tail")
     rec["phases_us_by_rows"] = {
         str(k): {"waves": len(v),
-                 names[0]: round(statistics.median(x[0] for x in v), 2),
-                 names[1]: round(statistics.median(x[1] for x in v), 2),
-                 names[2]: round(statistics.median(x[2] for x in v), 2),
+                 "warm": round(statistics.median(x[0] for x in v), 2),
+                 "steady": round(statistics.median(x[1] for x in v), 2),
+                 "tail": round(statistics.median(x[2] for x in v), 2),
                  "first_block": round(statistics.median(x[3] for x in v), 2),
                  "second_block": round(statistics.median(x[5] for x in v), 2),
                  "start_offset": round(statistics.median(x[4] for x in v), 2)}
