@@ -236,8 +236,11 @@ gol_status gol_reset_timing(gol_engine* e);
  * returns how many of those did so without stage logic: a unit whose neighbourhood
  * ended the launch before quiet copies its rows into the output buffer
  * (copy-through, on wherever the skip is; GOL_DEV_COPY_THROUGH=0 at create turns it
- * off and leaves the skip alone).  gol_activity_probed returns how many computed
- * units were found still by the first launch of a gol_step, which has no history:
+ * off and leaves the skip alone).  Before a step's second launch and its remainder
+ * launches a copy kernel of its own stores those rows and the launch only counts
+ * the units (the copy pass; the counters are the same with GOL_DEV_COPY_PASS=0 at
+ * create, which leaves the copying to the launch).  gol_activity_probed returns how
+ * many computed units were found still by the first launch of a gol_step, which has no history:
  * such a unit runs one generation over the rows it streams and, where that changes
  * nothing within depth - 1 cells of its rows, stores its input rows without the
  * other generations' stage logic (the still probe, on wherever the skip is;

@@ -295,6 +295,11 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
         e->through_on = !e->act_on ? 0 : !t ? 2 : std::max(0, std::min(2, std::atoi(t)));
         const char* x = std::getenv("GOL_DEV_STILL_EXIT");
         e->still_on = e->act_on && !(x && std::atoi(x) == 0);
+        // the copy pass: where copy-through is on, its rows move in a kernel of
+        // their own before a step's second launch and before its remainder launches
+        // (GOL_DEV_COPY_PASS=0 = off: the stencil kernel's copy loop, as before)
+        const char* cp = std::getenv("GOL_DEV_COPY_PASS");
+        e->pass_on = e->through_on >= 1 && !(cp && std::atoi(cp) == 0);
         // the still probe of a step's first launch (GOL_DEV_STILL_PROBE=0 = off)
         const char* pr = std::getenv("GOL_DEV_STILL_PROBE");
         e->probe_on = e->act_on && !(pr && std::atoi(pr) == 0);
@@ -623,6 +628,7 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     // always last) never skips and leaves the streaks alone: it reads the ones the
     // last depth-K launch wrote, and only to copy still units through (its depths
     // add up to less than K, so the lists, dilated by K, cover every one of them).
+    bool pass = false;  // the copy pass goes before this launch
     if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
         const ActState st{e->d_streak, (size_t)e->act_units};
         a.act = st.act();
@@ -643,15 +649,54 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             a.busy = e->still_on ? st.busy() : nullptr;
             a.launch_idx = e->act_launch;
             e->act_hist = par ^ 1;
+            // the step's second launch: its streaks are 0 or 1, no unit can skip
+            pass = a.through && e->act_launch == 1;
         } else if (may && depth < e->K && e->act_hist >= 0 && e->through_on >= 2) {
             a.streak_in = st.streak(e->act_hist);
             a.nb_off = p.d_nb;
             a.nb_ids = p.d_nb + p.nb_off.size();
             a.through = 1;
+            pass = true;  // a remainder launch never skips
         } else {
             e->act_hist = -1;
         }
         ++e->act_launch;
+    }
+    // Copy pass (life_copy.hip): the calm units' rows, stored by a kernel
+    // of its own on this stream (captured into the step's graph with the launch);
+    // the launch's calm units then store no row (through = 2).  Both read the same
+    // streaks, which neither writes before the launch's units have read them.
+    if (pass && e->pass_on && p.d_own && s == e->stream && p.segs.size() == 1) {
+        // The pass writes whole tiles, words of units that are not calm among them.
+        // That is safe only where every such unit stores its whole rectangle in
+        // the launch that follows: no unit of it may skip.  A remainder launch
+        // writes no streaks and never skips; a depth-K launch skips on streaks >= 2,
+        // which the step's second launch cannot see (the first wrote 0 or 1).
+        const bool none_skips = !a.streak_out || (a.launch_idx == 1 && !a.no_hist);
+        if (!none_skips || !a.streak_in || a.through != 1)
+            return fail(GOL_ESTATE, "copy pass before a launch whose units may skip");
+        const SegDesc& sg = p.segs[0];
+        gol::CopyArgs c{};
+        c.src = a.pbuf[0];
+        c.dst = a.pbuf[1];
+        c.owners = p.d_own;
+        c.calm = ActState{e->d_streak, (size_t)e->act_units}.calm();
+        c.streak_in = a.streak_in;
+        c.nb_off = a.nb_off;
+        c.nb_ids = a.nb_ids;
+        c.stride = a.stride;
+        c.base_row = sg.base_row;
+        c.lastmask = e->lastmask_split[0];
+        c.ntile = (int32_t)(p.owners.size() / gol::kCopyOwners);
+        c.ncol = p.copy_ncol;
+        c.total_units = (int32_t)p.total_units;
+        c.out_lo = (int32_t)sg.out_lo;
+        c.out_hi = (int32_t)sg.out_hi;
+        c.ng = (int32_t)e->ng;
+        c.vlo = (int32_t)std::max<int64_t>(0, -sg.glob0);
+        c.vhi = (int32_t)std::max<int64_t>(0, std::min(sg.in_rows, sg.field_h - sg.glob0));
+        HIP_TRY(gol::launch_copy_pass(c, s));
+        a.through = 2;
     }
 #if GOL_WAVE_LOG
     a.wlog = g_dev_wave_log;

@@ -64,7 +64,9 @@ struct ActState {
     uint32_t* busy() const { return base + 5 * units; }
     // per unit: first launches of a step that found it still after one generation
     uint32_t* probed() const { return base + 5 * units + 2; }
-    size_t words() const { return 6 * units + 2; }
+    // per unit: the copy pass's calm flags (life_copy.hip), rewritten by every pass
+    uint32_t* calm() const { return base + 6 * units + 2; }
+    size_t words() const { return 7 * units + 2; }
 };
 
 // gol_create splits GLOBAL fields of at least this many rows into 2 same-device
@@ -309,6 +311,11 @@ struct gol_engine {
         // device the offsets followed by the ids.  Empty: the plan never skips
         std::vector<uint32_t> nb_off, nb_ids;
         uint32_t* d_nb = nullptr;
+        // copy pass (life_copy.hip): the owners of its tiles, kCopyOwners slots per
+        // tile, uploaded next to d_nb.  Empty: the plan takes no pass
+        std::vector<uint32_t> owners;
+        uint32_t* d_own = nullptr;
+        int32_t copy_ncol = 0;
         // a copy of an earlier plan of the same rows (rank engines: the full-depth
         // launches of a round share one plan); its device tables are the owner's
         bool alias = false;
@@ -352,6 +359,8 @@ struct gol_engine {
     bool act_on = false;    // skip units at all
     int through_on = 0;     // copy-through: 0 = off, 1 = launches at depth K, 2 = the
                             // remainder launches too (GOL_DEV_COPY_THROUGH, default 2)
+    bool pass_on = false;   // the copy pass before a step's second launch and its
+                            // remainder launches (GOL_DEV_COPY_PASS=0 turns it off)
     bool still_on = false;  // the one-load exit (GOL_DEV_STILL_EXIT=0 turns it off)
     bool probe_on = false;  // the still probe (GOL_DEV_STILL_PROBE=0 turns it off)
 

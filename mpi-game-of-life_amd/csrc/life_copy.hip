@@ -1,0 +1,106 @@
+// life_copy.hip -- the copy pass (DESIGN §4 "Copy pass"): the rows of the calm
+// units of a stencil launch, moved from the launch's input buffer to its output
+// buffer by a kernel of its own instead of the copy loop inside life_tb_kernel.
+// That loop inherits the stencil kernel's shape (240 VGPRs, 2 wavefronts per SIMD,
+// one wavefront walking a unit's several hundred rows alone, 496-byte row pieces
+// that share 128-byte lines with the next strip); this kernel holds a few dozen
+// registers and no LDS, so it runs at full occupancy, gives every few rows to a
+// wavefront of their own, walks the field band by band, and writes whole lines.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "life_internal.h"
+
+namespace gol {
+
+namespace {
+
+// calm(U) as life_tb_kernel's prologue evaluates it: every streak_in of U's
+// neighbour list is >= 1, and an empty list is not calm (uniform).
+__device__ __forceinline__ bool unit_calm(const CopyArgs& a, uint32_t unit, int lane)
+{
+    const uint32_t o0 = a.nb_off[unit], o1 = a.nb_off[unit + 1];
+    bool calm = o1 > o0;
+    for (uint32_t j = o0; j < o1; j += 64) {
+        const uint32_t i = j + (uint32_t)lane;
+        const uint32_t st = i < o1 ? a.streak_in[a.nb_ids[i]] : 1u;
+        calm = calm && __builtin_amdgcn_ballot_w64(st < 1u) == 0;
+    }
+    return calm;
+}
+
+// The pass's first kernel: one wavefront per unit writes calm[unit] (1 or 0), so
+// that a tile's wavefront learns about its owners with two loads, not with a walk
+// of their lists: on a field in motion, where every tile leaves after that test,
+// the pass is bound by this chain of loads and nothing else.
+__global__ __launch_bounds__(256) void life_calm_kernel(CopyArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t unit =
+        blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (unit >= (uint32_t)a.total_units) return;
+    const bool calm = unit_calm(a, unit, lane);
+    if (lane == 0) a.calm[unit] = calm ? 1u : 0u;
+}
+
+// One wavefront per tile of kCopyTileRows rows x kCopyTileWords words, lane l = word
+// l of the tile's column segment, consecutive tiles along a row chunk.  The tile is
+// copied when one of its owners is calm, whole: the words of its other owners too.
+// Writing the words of a unit that is not calm is safe because the pass runs only
+// before launches none of whose units skips (engine.cpp launch checks it): such a
+// unit stores every word of its rectangle after the pass, on the same stream, from
+// the input buffer, which nobody writes.  A tile none of whose owners is calm is left
+// alone, so a field in motion costs the tiles' tests and no traffic.  The words
+// stored are the ones the stencil kernel's put_row(row_in()) stores: the last group
+// masked, rows outside [vlo, vhi) zero.  Loads and stores are non-temporal: each
+// word is touched once, and 2 x 537 MB at 65536^2 would only sweep the caches.  The
+// pass writes field words and its own calm flags, neither counters nor streaks.
+// Every index is checked against the tables' and the plan's bounds before any access.
+__global__ __launch_bounds__(256) void life_copy_kernel(CopyArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t tile =
+        blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (tile >= (uint32_t)a.ntile) return;
+    const uint32_t chunk = tile / (uint32_t)a.ncol, seg = tile - chunk * (uint32_t)a.ncol;
+    const int32_t rb = a.out_lo + (int32_t)chunk * kCopyTileRows;
+    const int32_t n = min(rb + kCopyTileRows, a.out_hi) - rb;
+    if (rb < 0 || n <= 0) return;
+    {
+        uint32_t c = 0;
+        if (lane < kCopyOwners) {
+            const uint32_t unit = a.owners[(size_t)tile * kCopyOwners + lane];
+            if (unit < (uint32_t)a.total_units) c = a.calm[unit];
+        }
+        if (__builtin_amdgcn_ballot_w64(c != 0u) == 0) return;
+    }
+    const int32_t q = (int32_t)seg * kCopyTileWords + lane;
+    if (q >= a.ng) return;
+    const uint64_t cm = q == a.ng - 1 ? a.lastmask : ~0ull;
+    const int64_t off = (a.base_row + rb) * a.stride + q;
+    const uint64_t* src = a.src + off;
+    uint64_t* dst = a.dst + off;
+    uint64_t g[kCopyTileRows];
+#pragma unroll
+    for (int j = 0; j < kCopyTileRows; ++j)
+        g[j] = __builtin_nontemporal_load(src + (int64_t)min(j, n - 1) * a.stride);
+#pragma unroll
+    for (int j = 0; j < kCopyTileRows; ++j) {
+        const bool ok = rb + j >= a.vlo && rb + j < a.vhi;
+        if (j < n) __builtin_nontemporal_store(ok ? (g[j] & cm) : 0ull, dst + (int64_t)j * a.stride);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_copy_pass(const CopyArgs& a, hipStream_t s)
+{
+    if (a.ntile <= 0 || a.ncol <= 0 || a.total_units <= 0) return hipSuccess;
+    const unsigned ublocks = ((unsigned)a.total_units + kWavesPerBlock - 1) / kWavesPerBlock;
+    hipLaunchKernelGGL(life_calm_kernel, dim3(ublocks), dim3(64 * kWavesPerBlock), 0, s, a);
+    const unsigned blocks = ((unsigned)a.ntile + kWavesPerBlock - 1) / kWavesPerBlock;
+    hipLaunchKernelGGL(life_copy_kernel, dim3(blocks), dim3(64 * kWavesPerBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace gol

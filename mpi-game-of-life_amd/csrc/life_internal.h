@@ -135,6 +135,10 @@ struct StepArgs {
     // runs one generation over its stream first and, where that equals the input
     // on its rectangles dilated by depth - 1, stores its input rows and ends quiet;
     // it counts in act as computed and in probed[unit], not in copied.
+    // Copy pass (`through` = 2; life_copy.hip): life_copy_kernel, enqueued
+    // directly before this launch on the same stream, has already stored the rows of
+    // every unit whose list has streak_in >= 1 throughout; such a unit writes its
+    // streak, busy[1] and its counters as under `through` = 1 and stores no row.
     const uint32_t* streak_in;
     uint32_t* streak_out;
     const uint32_t* nb_off;
@@ -215,6 +219,38 @@ constexpr int handoff_toff(int64_t R, int K, int planes)
 hipError_t launch_life(const StepArgs& a, int depth, RuleKind rule, int planes, bool hand,
                        hipStream_t s);
 bool life_has_kernel(int depth, int planes);
+
+// The copy pass (life_copy.hip, DESIGN §4 "Copy pass"): two low-register kernels
+// that store the rows of the calm units (neighbour list all streak_in >= 1) of a
+// one-segment plan of 2-plane groups from `src` to `dst`, for the stencil launch
+// that follows them with StepArgs::through = 2.  The first writes calm[unit] for
+// every unit.  The second works on line-aligned tiles of the segment's output rows,
+// kCopyTileRows rows x kCopyTileWords words (512 bytes: every 128-byte line of a row
+// is written by one wavefront), tile t = row chunk t / ncol, column segment
+// t % ncol, and takes from a device table the units with a rectangle (plan.cpp
+// unit_rects) that meets each tile: its owners, kCopyOwners slots per tile, the
+// unused ones ~0.
+constexpr int kCopyTileRows = 8;
+constexpr int kCopyTileWords = 64;
+constexpr int kCopyOwners = 8;
+struct CopyArgs {
+    const uint64_t* src;  // row 0 of the launch's pbuf[0] and pbuf[1]
+    uint64_t* dst;
+    const uint32_t* owners;     // ntile x kCopyOwners unit indices
+    uint32_t* calm;             // total_units words, written by the pass's first kernel
+    const uint32_t* streak_in;  // as the launch that follows reads them
+    const uint32_t* nb_off;
+    const uint32_t* nb_ids;
+    int64_t stride;    // words per buffer row
+    int64_t base_row;  // buffer row of the segment's local row 0
+    uint64_t lastmask; // stored-form valid bits of group ng - 1
+    int32_t ntile, ncol;
+    int32_t total_units;
+    int32_t out_lo, out_hi;  // the segment's output rows (local)
+    int32_t ng;
+    int32_t vlo, vhi;  // local rows inside the buffer and the field; others store 0
+};
+hipError_t launch_copy_pass(const CopyArgs& a, hipStream_t s);
 
 // Resident 256-thread blocks per CU of the stencil kernel (occupancy query).
 // mp: of the multi-pass kernels (0 where none exists)

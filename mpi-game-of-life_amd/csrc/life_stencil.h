@@ -809,7 +809,11 @@ void life_tb_kernel(StepArgs a)
             };
             // (two chunks in turn, the next one's loads issued before this one's
             // stores, measured no faster: profiles/r08/ab_copy_pipelined_rejected.jsonl)
-            for (int32_t r0 = 0; r0 < n; r0 += kCopyRows) {
+            // Copy pass (`through` = 2): life_copy_kernel, which ran the same calm test
+            // on the same streaks directly before this launch, has stored the rows;
+            // what is left is what follows the loop.  (The test sits here and not in
+            // the prologue, where it cost the B3/S23 classic kernel 1 % on a soup.)
+            for (int32_t r0 = 0; r0 < n && a.through != 2; r0 += kCopyRows) {
                 Grp<NP> g[kCopyRows];
                 load_rows(g, r0);
                 store_rows(g, r0);

@@ -379,6 +379,8 @@ void free_plan(gol_engine::Plan& q)
     if (q.dev) (void)hipFree(q.dev);
     if (q.dpairs) (void)hipFree(q.dpairs);
     if (q.d_nb) (void)hipFree(q.d_nb);
+    if (q.d_own) (void)hipFree(q.d_own);
+    q.d_own = nullptr;
     q.dev = nullptr;
     q.dpairs = nullptr;
     q.d_nb = nullptr;
@@ -480,6 +482,44 @@ void build_neighbours(gol_engine::Plan& p, int64_t ng, int K)
         p.nb_ids.insert(p.nb_ids.end(), mine.begin(), mine.end());
         p.nb_off[(size_t)u + 1] = (uint32_t)p.nb_ids.size();
     }
+}
+
+// The copy pass's table (life_copy.hip): the segment's output rows in tiles of
+// kCopyTileRows rows x kCopyTileWords words, row chunks from out_lo, column segments
+// fastest; per tile the units one of whose rectangles (unit_rects) meets it, in
+// kCopyOwners slots (~0: unused).  The rectangles tile the output rows
+// (tests/test_activity_neighbours.py), so every word of a tile has an owner among
+// them.  Left empty (no pass) where a tile has more owners than slots (row blocks of
+// a few rows) or the indices would not fit 32 bits.
+static void build_copy_owners(gol_engine::Plan& p, int64_t ng)
+{
+    p.owners.clear();
+    p.copy_ncol = 0;
+    const int64_t lim = int64_t(1) << 27;
+    if (p.segs.size() != 1 || p.segs[0].out_hi >= 8 * lim || ng >= lim) return;
+    const SegDesc& sg = p.segs[0];
+    const int64_t R = gol::kCopyTileRows, C = gol::kCopyTileWords, S = gol::kCopyOwners;
+    const int64_t ncol = (ng + C - 1) / C, nrow = (std::max(sg.out_hi, sg.out_lo) - sg.out_lo + R - 1) / R;
+    if (ncol * nrow <= 0 || ncol * nrow >= lim) return;
+    std::vector<URect> rc;
+    unit_rects(p, ng, rc);
+    std::vector<uint32_t> own((size_t)(ncol * nrow * S), ~0u);
+    for (int64_t u = 0; u < p.total_units; ++u)
+        for (int k = 0; k < 2; ++k) {
+            const URect& r = rc[(size_t)(2 * u + k)];
+            if (r.r1 <= r.r0 || r.q1 <= r.q0) continue;
+            if (r.r0 < sg.out_lo || r.r1 > sg.out_hi || r.q0 < 0 || r.q1 > ng) return;
+            for (int64_t i = (r.r0 - sg.out_lo) / R; i <= (r.r1 - 1 - sg.out_lo) / R; ++i)
+                for (int64_t c = r.q0 / C; c <= (r.q1 - 1) / C; ++c) {
+                    uint32_t* slot = &own[(size_t)((i * ncol + c) * S)];
+                    int64_t j = 0;
+                    while (j < S && slot[j] != ~0u && slot[j] != (uint32_t)u) ++j;
+                    if (j == S) return;
+                    slot[j] = (uint32_t)u;
+                }
+        }
+    p.owners.swap(own);
+    p.copy_ncol = (int32_t)ncol;
 }
 
 gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& raw)
@@ -715,6 +755,7 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
                               !(p.hand && p.multi_blk) && p.total_units > 0 &&
                               p.total_units < (int64_t(1) << 28);
         if (act_plan) build_neighbours(p, (int64_t)e->ng, (int)e->K);
+        if (act_plan && e->planes == 2) build_copy_owners(p, (int64_t)e->ng);
         max_units = std::max(max_units, p.total_units);
         any_hand |= p.hand && p.multi_blk;
         any_mp |= p.npass > 1;
@@ -742,6 +783,11 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
                               hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(p.d_nb + p.nb_off.size(), p.nb_ids.data(),
                               sizeof(uint32_t) * p.nb_ids.size(), hipMemcpyHostToDevice));
+        }
+        if (!p.nb_off.empty() && !p.owners.empty()) {
+            HIP_TRY(hipMalloc(&p.d_own, sizeof(uint32_t) * p.owners.size()));
+            HIP_TRY(hipMemcpy(p.d_own, p.owners.data(), sizeof(uint32_t) * p.owners.size(),
+                              hipMemcpyHostToDevice));
         }
         return GOL_OK;
     };
