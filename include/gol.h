@@ -245,11 +245,18 @@ gol_status gol_reset_timing(gol_engine* e);
  * nothing within depth - 1 cells of its rows, stores its input rows without the
  * other generations' stage logic (the still probe, on wherever the skip is;
  * GOL_DEV_STILL_PROBE=0 at create turns it off); these units are not counted as
- * copied.  Any out pointer may be NULL.  Composite engines, group members and rank
+ * copied.  gol_activity_elided returns how many calm units the copy pass left
+ * alone because the buffer it writes already held their rows: units that probed
+ * through in the step's first launch (before the second launch), units still for
+ * two launches (before a remainder launch), and every calm unit of the second and
+ * later launches of one remainder.  The launch after the pass counts them as
+ * computed and copied all the same; GOL_DEV_COPY_ELIDE=0 at create makes the pass
+ * copy them as before (the count stays 0).  Any out pointer may be NULL.  Composite engines, group members and rank
  * engines of more than one rank keep no counters: all 0. */
 gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units);
 gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units);
 gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units);
+gol_status gol_activity_elided(gol_engine* e, uint64_t* elided_units);
 
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */

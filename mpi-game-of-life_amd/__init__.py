@@ -39,7 +39,7 @@ EXPORTS = [
     "gol_plan_resident", "gol_plan_skew", "gol_plan_columns", "gol_plan_tuning",
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
-    "gol_activity_copied", "gol_activity_probed", "gol_torus_geometry", "gol_torus_pad",
+    "gol_activity_copied", "gol_activity_probed", "gol_activity_elided", "gol_torus_geometry", "gol_torus_pad",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
 ]
 
@@ -201,6 +201,7 @@ def lib():
     L.gol_activity.argtypes = [vp, pu64, pu64]
     L.gol_activity_copied.argtypes = [vp, pu64]
     L.gol_activity_probed.argtypes = [vp, pu64]
+    L.gol_activity_elided.argtypes = [vp, pu64]
     L.gol_plan_neighbours.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, vp, u64,
                                       vp, u64, pu64, pu64]
     L.gol_torus_geometry.argtypes = [u64, u64, ctypes.POINTER(Config), ctypes.POINTER(u32),
@@ -221,7 +222,8 @@ def lib():
                  "gol_create_rank_transport", "gol_round_schedule", "gol_plan_tuning",
                  "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
                  "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity",
-                 "gol_plan_neighbours", "gol_activity_copied", "gol_activity_probed"]:
+                 "gol_plan_neighbours", "gol_activity_copied", "gol_activity_probed",
+                 "gol_activity_elided"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -562,6 +564,14 @@ class Engine:
         gol_activity_probed).  Not counted in activity_copied()."""
         c = ctypes.c_uint64()
         _check(lib().gol_activity_probed(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_elided(self):
+        """Calm units whose rows the copy pass left alone because its destination
+        already held them (gol_activity_elided).  They stay counted in activity()
+        and activity_copied() by the launch that follows the pass."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_elided(self._h, ctypes.byref(c)))
         return c.value
 
     def timing(self):

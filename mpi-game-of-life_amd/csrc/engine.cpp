@@ -303,6 +303,10 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
         // the still probe of a step's first launch (GOL_DEV_STILL_PROBE=0 = off)
         const char* pr = std::getenv("GOL_DEV_STILL_PROBE");
         e->probe_on = e->act_on && !(pr && std::atoi(pr) == 0);
+        // copy elision: the pass leaves the rows its destination already holds
+        // (GOL_DEV_COPY_ELIDE=0 = off: the pass copies every calm unit, as before)
+        const char* el = std::getenv("GOL_DEV_COPY_ELIDE");
+        e->elide_on = e->pass_on && !(el && std::atoi(el) == 0);
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return GOL_OK;
@@ -629,6 +633,9 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     // last depth-K launch wrote, and only to copy still units through (its depths
     // add up to less than K, so the lists, dilated by K, cover every one of them).
     bool pass = false;  // the copy pass goes before this launch
+    // copy elision: the pass may take ActState::held (case P) / every calm unit's
+    // rows are in the output buffer already (case R)
+    bool pass_held = false, pass_all = false;
     if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
         const ActState st{e->d_streak, (size_t)e->act_units};
         a.act = st.act();
@@ -645,20 +652,32 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             a.no_hist = e->act_launch == 0 ? 1 : 0;
             a.probe = (a.no_hist && e->probe_on) ? 1 : 0;
             a.probed = st.probed();
+            // (copy elision) a first launch that probes writes every unit's flag
+            a.held = (a.probe && e->elide_on) ? st.held() : nullptr;
+            if (a.no_hist) e->act_probed = a.held != nullptr;
             a.through = e->through_on >= 1 ? 1 : 0;
             a.busy = e->still_on ? st.busy() : nullptr;
             a.launch_idx = e->act_launch;
             e->act_hist = par ^ 1;
             // the step's second launch: its streaks are 0 or 1, no unit can skip
             pass = a.through && e->act_launch == 1;
+            pass_held = e->act_probed;
         } else if (may && depth < e->K && e->act_hist >= 0 && e->through_on >= 2) {
             a.streak_in = st.streak(e->act_hist);
             a.nb_off = p.d_nb;
             a.nb_ids = p.d_nb + p.nb_off.size();
             a.through = 1;
             pass = true;  // a remainder launch never skips
+            // the step's second launch: the first one's input is this one's output
+            pass_held = e->act_probed && e->act_launch == 1;
+            // a later launch of the same remainder: the same streaks, the buffers
+            // swapped, and every calm unit's rows went across (or were there) in the
+            // launch before
+            pass_all = e->act_rem > 0;
+            ++e->act_rem;
         } else {
             e->act_hist = -1;
+            e->act_probed = false;
         }
         ++e->act_launch;
     }
@@ -680,7 +699,12 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         c.src = a.pbuf[0];
         c.dst = a.pbuf[1];
         c.owners = p.d_own;
-        c.calm = ActState{e->d_streak, (size_t)e->act_units}.calm();
+        const ActState st{e->d_streak, (size_t)e->act_units};
+        c.need = st.need();
+        // copy elision (GOL_DEV_COPY_ELIDE=0: elided null, every calm unit copies)
+        c.elided = e->elide_on ? st.elided() : nullptr;
+        c.held = (e->elide_on && pass_held) ? st.held() : nullptr;
+        c.all_held = (e->elide_on && pass_all) ? 1 : 0;
         c.streak_in = a.streak_in;
         c.nb_off = a.nb_off;
         c.nb_ids = a.nb_ids;
@@ -1312,9 +1336,13 @@ gol_status step_single(gol_engine* e, uint64_t generations)
     // numbers them from 0
     e->act_launch = 0;
     e->act_hist = -1;
+    e->act_probed = false;
+    e->act_rem = 0;
     const gol_status st = step_single_launches(e, generations);
     e->act_launch = -1;
     e->act_hist = -1;
+    e->act_probed = false;
+    e->act_rem = 0;
     return st;
 }
 
@@ -1673,7 +1701,7 @@ static gol_status rect_bounds(const gol_engine* e, uint64_t y, uint64_t x, uint6
 // The activity counters of an engine, summed over its units (and over the parts
 // of a composite engine), after everything issued on its stream has run.
 struct ActTotals {
-    uint64_t computed = 0, skipped = 0, copied = 0, probed = 0;
+    uint64_t computed = 0, skipped = 0, copied = 0, probed = 0, elided = 0;
 };
 static gol_status read_activity(gol_engine* e, ActTotals& t)
 {
@@ -1691,6 +1719,7 @@ static gol_status read_activity(gol_engine* e, ActTotals& t)
         t.skipped += st.act()[2 * u + 1];
         t.copied += st.copied()[u];
         t.probed += st.probed()[u];
+        t.elided += st.elided()[u];
     }
     // launches that every unit skipped at the one-load exit (only plan 0's
     // launches of a step ever skip)
@@ -1889,13 +1918,15 @@ gol_status gol_reset_timing(gol_engine* e)
     if (e->d_streak) {
         HIP_TRY(hipSetDevice(e->device));
         // Every counter: computed / skipped, copied and busy[0] lie one after the
-        // other, the probed ones behind busy[1].  The streaks and busy[1] are not
+        // other, the probed ones behind busy[1], the elided ones behind the pass's and
+        // the probe's flags.  The streaks, the flags and busy[1] are not
         // statistics but the skip's own state within a step, which each step's
         // first launch starts afresh: a reset leaves them alone.
         const ActState as{e->d_streak, (size_t)e->act_units};
         HIP_TRY(hipMemsetAsync(as.act(), 0, (size_t)(as.busy() + 1 - as.act()) * sizeof(uint32_t),
                                e->stream));
         HIP_TRY(hipMemsetAsync(as.probed(), 0, as.units * sizeof(uint32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(as.elided(), 0, as.units * sizeof(uint32_t), e->stream));
     }
     return GOL_OK;
 }
@@ -1906,6 +1937,15 @@ gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units)
     ActTotals t;
     GOL_TRY(read_activity(e, t));
     if (probed_units) *probed_units = t.probed;
+    return GOL_OK;
+}
+
+gol_status gol_activity_elided(gol_engine* e, uint64_t* elided_units)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    ActTotals t;
+    GOL_TRY(read_activity(e, t));
+    if (elided_units) *elided_units = t.elided;
     return GOL_OK;
 }
 

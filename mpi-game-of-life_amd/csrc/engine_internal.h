@@ -64,9 +64,15 @@ struct ActState {
     uint32_t* busy() const { return base + 5 * units; }
     // per unit: first launches of a step that found it still after one generation
     uint32_t* probed() const { return base + 5 * units + 2; }
-    // per unit: the copy pass's calm flags (life_copy.hip), rewritten by every pass
-    uint32_t* calm() const { return base + 6 * units + 2; }
-    size_t words() const { return 7 * units + 2; }
+    // per unit: the copy pass's flags (life_copy.hip: calm and its rows to be moved),
+    // rewritten by every pass
+    uint32_t* need() const { return base + 6 * units + 2; }
+    // per unit: 1 = took the still probe's quiet exit in the step's first launch,
+    // rewritten by every launch that probes
+    uint32_t* held() const { return base + 7 * units + 2; }
+    // per unit: passes that found it calm with its rows already in the destination
+    uint32_t* elided() const { return base + 8 * units + 2; }
+    size_t words() const { return 9 * units + 2; }
 };
 
 // gol_create splits GLOBAL fields of at least this many rows into 2 same-device
@@ -355,6 +361,10 @@ struct gol_engine {
     int64_t act_units = 0;
     int act_launch = -1;
     int act_hist = -1;
+    // the step's first launch probed and wrote ActState::held for every unit; the
+    // remainder launches of the step issued so far (copy elision)
+    bool act_probed = false;
+    int act_rem = 0;
     // what the engine may do, decided at create:
     bool act_on = false;    // skip units at all
     int through_on = 0;     // copy-through: 0 = off, 1 = launches at depth K, 2 = the
@@ -363,6 +373,8 @@ struct gol_engine {
                             // remainder launches (GOL_DEV_COPY_PASS=0 turns it off)
     bool still_on = false;  // the one-load exit (GOL_DEV_STILL_EXIT=0 turns it off)
     bool probe_on = false;  // the still probe (GOL_DEV_STILL_PROBE=0 turns it off)
+    bool elide_on = false;  // the copy pass leaves rows its destination already holds
+                            // (GOL_DEV_COPY_ELIDE=0 turns it off)
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on

@@ -16,45 +16,64 @@ namespace gol {
 namespace {
 
 // calm(U) as life_tb_kernel's prologue evaluates it: every streak_in of U's
-// neighbour list is >= 1, and an empty list is not calm (uniform).
-__device__ __forceinline__ bool unit_calm(const CopyArgs& a, uint32_t unit, int lane)
+// neighbour list is >= 1, and an empty list is not calm (uniform); *still: every
+// one of them is >= 2, the condition on which a depth-K launch skips U.
+__device__ __forceinline__ bool unit_calm(const CopyArgs& a, uint32_t unit, int lane, bool* still)
 {
     const uint32_t o0 = a.nb_off[unit], o1 = a.nb_off[unit + 1];
-    bool calm = o1 > o0;
+    bool calm = o1 > o0, st2 = o1 > o0;
     for (uint32_t j = o0; j < o1; j += 64) {
         const uint32_t i = j + (uint32_t)lane;
-        const uint32_t st = i < o1 ? a.streak_in[a.nb_ids[i]] : 1u;
+        const uint32_t st = i < o1 ? a.streak_in[a.nb_ids[i]] : 2u;
         calm = calm && __builtin_amdgcn_ballot_w64(st < 1u) == 0;
+        st2 = st2 && __builtin_amdgcn_ballot_w64(st < 2u) == 0;
     }
+    *still = st2;
     return calm;
 }
 
-// The pass's first kernel: one wavefront per unit writes calm[unit] (1 or 0), so
+// The pass's first kernel: one wavefront per unit writes need[unit] (1 or 0), so
 // that a tile's wavefront learns about its owners with two loads, not with a walk
 // of their lists: on a field in motion, where every tile leaves after that test,
 // the pass is bound by this chain of loads and nothing else.
+// Copy elision (DESIGN §4 "Copy pass"): need = calm and the destination does not hold
+// the unit's rows yet.  It holds them (a.elided set) when the unit probed through
+// in the step's first launch and this pass goes before the second (a.held: dst was
+// that launch's input, which the probe proved equal to its output on the unit),
+// when the unit is still (it was calm in the launch before, whose input buffer is
+// dst and whose output it left equal to it), or in every calm unit of the second
+// and later launches of one remainder (a.all_held).  Only this kernel writes
+// elided[], one lane per unit.
 __global__ __launch_bounds__(256) void life_calm_kernel(CopyArgs a)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t unit =
         blockIdx.x * (uint32_t)kWavesPerBlock + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (unit >= (uint32_t)a.total_units) return;
-    const bool calm = unit_calm(a, unit, lane);
-    if (lane == 0) a.calm[unit] = calm ? 1u : 0u;
+    bool still;
+    const bool calm = unit_calm(a, unit, lane, &still);
+    if (lane == 0) {
+        const bool holds =
+            a.elided && (a.all_held || still || (a.held && a.held[unit] != 0u));
+        a.need[unit] = (calm && !holds) ? 1u : 0u;
+        if (calm && holds) a.elided[unit] += 1u;
+    }
 }
 
 // One wavefront per tile of kCopyTileRows rows x kCopyTileWords words, lane l = word
 // l of the tile's column segment, consecutive tiles along a row chunk.  The tile is
-// copied when one of its owners is calm, whole: the words of its other owners too.
-// Writing the words of a unit that is not calm is safe because the pass runs only
+// copied when one of its owners has `need`, whole: the words of its other owners too.
+// Writing the words of a calm unit whose rows dst holds stores equal values; writing
+// the words of a unit that is not calm is safe because the pass runs only
 // before launches none of whose units skips (engine.cpp launch checks it): such a
 // unit stores every word of its rectangle after the pass, on the same stream, from
-// the input buffer, which nobody writes.  A tile none of whose owners is calm is left
+// the input buffer, which nobody writes.  A tile none of whose owners has `need` is left
 // alone, so a field in motion costs the tiles' tests and no traffic.  The words
 // stored are the ones the stencil kernel's put_row(row_in()) stores: the last group
 // masked, rows outside [vlo, vhi) zero.  Loads and stores are non-temporal: each
 // word is touched once, and 2 x 537 MB at 65536^2 would only sweep the caches.  The
-// pass writes field words and its own calm flags, neither counters nor streaks.
+// pass writes field words, its own need flags and the elided counters, no other
+// counter and no streak.
 // Every index is checked against the tables' and the plan's bounds before any access.
 __global__ __launch_bounds__(256) void life_copy_kernel(CopyArgs a)
 {
@@ -70,7 +89,7 @@ __global__ __launch_bounds__(256) void life_copy_kernel(CopyArgs a)
         uint32_t c = 0;
         if (lane < kCopyOwners) {
             const uint32_t unit = a.owners[(size_t)tile * kCopyOwners + lane];
-            if (unit < (uint32_t)a.total_units) c = a.calm[unit];
+            if (unit < (uint32_t)a.total_units) c = a.need[unit];
         }
         if (__builtin_amdgcn_ballot_w64(c != 0u) == 0) return;
     }
@@ -98,6 +117,7 @@ hipError_t launch_copy_pass(const CopyArgs& a, hipStream_t s)
     if (a.ntile <= 0 || a.ncol <= 0 || a.total_units <= 0) return hipSuccess;
     const unsigned ublocks = ((unsigned)a.total_units + kWavesPerBlock - 1) / kWavesPerBlock;
     hipLaunchKernelGGL(life_calm_kernel, dim3(ublocks), dim3(64 * kWavesPerBlock), 0, s, a);
+    if (a.all_held && a.elided) return hipGetLastError();
     const unsigned blocks = ((unsigned)a.ntile + kWavesPerBlock - 1) / kWavesPerBlock;
     hipLaunchKernelGGL(life_copy_kernel, dim3(blocks), dim3(64 * kWavesPerBlock), 0, s, a);
     return hipGetLastError();

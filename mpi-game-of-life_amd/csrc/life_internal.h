@@ -139,6 +139,9 @@ struct StepArgs {
     // directly before this launch on the same stream, has already stored the rows of
     // every unit whose list has streak_in >= 1 throughout; such a unit writes its
     // streak, busy[1] and its counters as under `through` = 1 and stores no row.
+    // Copy elision (`held`, set with probe or null): every unit of a probing launch
+    // writes held[unit], 1 where it took the probe's quiet exit, else 0; the pass
+    // before the step's second launch reads it (CopyArgs::held).
     const uint32_t* streak_in;
     uint32_t* streak_out;
     const uint32_t* nb_off;
@@ -151,6 +154,7 @@ struct StepArgs {
     int32_t probe;
     int32_t through;
     int32_t launch_idx;
+    uint32_t* held;
 };
 constexpr uint32_t kStreakCap = 255;
 
@@ -230,6 +234,13 @@ bool life_has_kernel(int depth, int planes);
 // t % ncol, and takes from a device table the units with a rectangle (plan.cpp
 // unit_rects) that meets each tile: its owners, kCopyOwners slots per tile, the
 // unused ones ~0.
+// Copy elision (DESIGN §4 "Copy pass"): the first kernel also finds the calm units
+// whose rows `dst` already holds -- probed through in the step's first launch
+// (`held`, non-null only before the step's second launch after a first launch that
+// probed), every streak_in of the list >= 2, or all of them in the second and later
+// launches of one remainder (`all_held`, which run the first kernel alone) -- counts
+// them in elided[unit] and writes need[unit] = calm and not held; the second copies
+// a tile when one of its owners has `need`.
 constexpr int kCopyTileRows = 8;
 constexpr int kCopyTileWords = 64;
 constexpr int kCopyOwners = 8;
@@ -237,7 +248,10 @@ struct CopyArgs {
     const uint64_t* src;  // row 0 of the launch's pbuf[0] and pbuf[1]
     uint64_t* dst;
     const uint32_t* owners;     // ntile x kCopyOwners unit indices
-    uint32_t* calm;             // total_units words, written by the pass's first kernel
+    uint32_t* need;             // total_units words, written by the pass's first kernel
+    const uint32_t* held;       // StepArgs::held of the step's first launch, or null
+    uint32_t* elided;           // per-unit counter, or null: no elision (every calm unit copies)
+    int32_t all_held;           // every calm unit's rows are in dst: no tile kernel
     const uint32_t* streak_in;  // as the launch that follows reads them
     const uint32_t* nb_off;
     const uint32_t* nb_ids;

@@ -837,6 +837,10 @@ void life_tb_kernel(StepArgs a)
         // the unit's output rows are its input rows and it ends the launch quiet.
         // The input rows of [rb, re) are stored as they pass; the first chunk with a
         // difference leaves for the compute path below, which stores every row again.
+        // Copy elision (StepArgs::held): every unit of a probing launch writes its
+        // flag, 1 on the quiet exit and else 0 (here for a unit without rows, which
+        // does not probe), so that no flag of an earlier step survives the launch.
+        if (a.probe && a.held && n <= 0 && lane == 0) a.held[unit] = 0u;
         if (a.probe && a.streak_out && a.no_hist && n > 0) {
             // rows per chunk (even: a chunk starts at an even step).  4 where 16
             // would cost the kernel registers it does not otherwise need: the
@@ -916,9 +920,11 @@ void life_tb_kernel(StepArgs a)
                     a.streak_out[unit] = min(streak + 1u, kStreakCap);
                     if (a.act) a.act[2 * unit] += 1u;
                     if (a.probed) a.probed[unit] += 1u;
+                    if (a.held) a.held[unit] = 1u;
                 }
                 return;
             }
+            if (a.held && lane == 0) a.held[unit] = 0u;
         }
     }
     for (int pass = 0; pass < npass; ++pass) {
