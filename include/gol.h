@@ -257,6 +257,15 @@ gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipp
 gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units);
 gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units);
 gol_status gol_activity_elided(gol_engine* e, uint64_t* elided_units);
+/* The probe pass: before a step's first launch a kernel of its own runs that one
+ * generation over line-aligned tiles of the field (the copy pass's tiles), stores the
+ * tiles that keep their state and marks the units near a tile that does not.  A unit
+ * it leaves unmarked is found still by the launch on that word alone;
+ * gol_activity_pass_probed returns how many of the units gol_activity_probed counts
+ * went through that way.  The pass changes no other counter and no field word; it
+ * runs wherever the copy pass does, and GOL_DEV_PROBE_PASS=0 at create turns it off
+ * (the count stays 0). */
+gol_status gol_activity_pass_probed(gol_engine* e, uint64_t* pass_probed_units);
 
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */
@@ -512,6 +521,20 @@ gol_status gol_plan_neighbours(uint64_t h, uint64_t w, const gol_config* cfg, in
                                int occ_classic, int occ_hand, int64_t* rects,
                                uint32_t* offsets, uint64_t unit_cap, uint32_t* ids,
                                uint64_t id_cap, uint64_t* units, uint64_t* nids);
+
+/* Host-only, same model: the probe pass's table of that plan.  The plan's output
+ * rows are cut into tiles of *tile_rows rows x *tile_words 64-column words, row
+ * chunks from the first output row, *ncol column segments per chunk fastest; per
+ * tile *slots unit indices in `table` (unused slots ~0): every unit one of whose
+ * rectangles (gol_plan_neighbours), dilated by depth - 1 cells and clipped to the
+ * field, meets the tile.  *ntile returns the tile count, 0 for a plan without the
+ * pass (no copy pass, or a tile with more units than slots); `table` is filled only
+ * when cap >= *ntile x *slots words (pass NULL and 0 to ask).  tile_rows, tile_words
+ * and slots may be NULL. */
+gol_status gol_plan_probe_tiles(uint64_t h, uint64_t w, const gol_config* cfg, int cus,
+                                int occ_classic, int occ_hand, uint32_t* table, uint64_t cap,
+                                uint32_t* tile_rows, uint32_t* tile_words, uint32_t* slots,
+                                uint64_t* ntile, uint64_t* ncol);
 
 /* ---- Torus geometry and wrap rule, host-only (no GPU needed) ---- */
 

@@ -40,6 +40,7 @@ EXPORTS = [
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
     "gol_activity_copied", "gol_activity_probed", "gol_activity_elided", "gol_torus_geometry", "gol_torus_pad",
+    "gol_activity_pass_probed", "gol_plan_probe_tiles",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
 ]
 
@@ -202,6 +203,10 @@ def lib():
     L.gol_activity_copied.argtypes = [vp, pu64]
     L.gol_activity_probed.argtypes = [vp, pu64]
     L.gol_activity_elided.argtypes = [vp, pu64]
+    L.gol_activity_pass_probed.argtypes = [vp, pu64]
+    L.gol_plan_probe_tiles.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, u64,
+                                       ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                       ctypes.POINTER(u32), pu64, pu64]
     L.gol_plan_neighbours.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, vp, u64,
                                       vp, u64, pu64, pu64]
     L.gol_torus_geometry.argtypes = [u64, u64, ctypes.POINTER(Config), ctypes.POINTER(u32),
@@ -223,7 +228,7 @@ def lib():
                  "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
                  "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity",
                  "gol_plan_neighbours", "gol_activity_copied", "gol_activity_probed",
-                 "gol_activity_elided"]:
+                 "gol_activity_elided", "gol_activity_pass_probed", "gol_plan_probe_tiles"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -310,6 +315,26 @@ def plan_neighbours(h, w, cus=256, occ_classic=2, occ_hand=2, **cfg_kw):
                                      ids.ctypes.data, ni.value, ctypes.byref(nu),
                                      ctypes.byref(ni)))
     return rects, offs, ids[:ni.value]
+
+
+def plan_probe_tiles(h, w, cus=256, occ_classic=2, occ_hand=2, **cfg_kw):
+    """gol_plan_probe_tiles (host only, no GPU): the probe pass's table of the launch
+    plan gol_create would build.  Returns (tile_rows, tile_words, ncol, table): the
+    plan's output rows in tiles of tile_rows rows x tile_words 64-column words, ncol
+    column segments per row chunk fastest; table a uint32 array [tiles, slots] of
+    unit indices (unused slots 0xFFFFFFFF), or None for a plan without the pass."""
+    import numpy as np
+    cfg = make_config(**cfg_kw)
+    tr, tw, sl = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    nt, nc = ctypes.c_uint64(), ctypes.c_uint64()
+    args = (h, w, ctypes.byref(cfg), cus, occ_classic, occ_hand)
+    outs = (ctypes.byref(tr), ctypes.byref(tw), ctypes.byref(sl), ctypes.byref(nt), ctypes.byref(nc))
+    _check(lib().gol_plan_probe_tiles(*args, None, 0, *outs))
+    if nt.value == 0:
+        return tr.value, tw.value, 0, None
+    table = np.zeros((nt.value, sl.value), dtype=np.uint32)
+    _check(lib().gol_plan_probe_tiles(*args, table.ctypes.data, table.size, *outs))
+    return tr.value, tw.value, nc.value, table
 
 
 def torus_geometry(h, w, **cfg_kw):
@@ -564,6 +589,13 @@ class Engine:
         gol_activity_probed).  Not counted in activity_copied()."""
         c = ctypes.c_uint64()
         _check(lib().gol_activity_probed(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_pass_probed(self):
+        """Units counted by activity_probed() that went through on the probe pass's
+        word, without a field load in the launch (gol_activity_pass_probed)."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_pass_probed(self._h, ctypes.byref(c)))
         return c.value
 
     def activity_elided(self):

@@ -307,6 +307,10 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
         // (GOL_DEV_COPY_ELIDE=0 = off: the pass copies every calm unit, as before)
         const char* el = std::getenv("GOL_DEV_COPY_ELIDE");
         e->elide_on = e->pass_on && !(el && std::atoi(el) == 0);
+        // the probe pass: the first launch's still probe, run tile by tile in a kernel
+        // of its own before it (GOL_DEV_PROBE_PASS=0 = off: the in-kernel probe alone)
+        const char* pp = std::getenv("GOL_DEV_PROBE_PASS");
+        e->ppass_on = e->probe_on && !(pp && std::atoi(pp) == 0);
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return GOL_OK;
@@ -722,6 +726,38 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         HIP_TRY(gol::launch_copy_pass(c, s));
         a.through = 2;
     }
+    // Probe pass (life_probe.hip): before a step's first launch, where that
+    // launch probes, under the copy pass's conditions.  The launch has no history, so
+    // none of its units skips or copies: a unit the pass leaves unmarked ends quiet on
+    // the pass's word, every other one stores its whole rectangle after the pass.
+    if (a.probe && e->ppass_on && p.d_ptab && s == e->stream && p.segs.size() == 1 &&
+        e->planes == 2) {
+        if (!a.no_hist || !a.streak_out)
+            return fail(GOL_ESTATE, "probe pass before a launch with history");
+        const SegDesc& sg = p.segs[0];
+        const ActState st{e->d_streak, (size_t)e->act_units};
+        gol::ProbeArgs c{};
+        c.src = a.pbuf[0];
+        c.dst = a.pbuf[1];
+        c.tiles = p.d_ptab;
+        c.moved = st.moved();
+        c.stride = a.stride;
+        c.base_row = sg.base_row;
+        c.lastmask = e->lastmask_split[0];
+        c.ntile = (int32_t)(p.probe_tiles.size() / gol::kProbeSlots);
+        c.ncol = p.copy_ncol;
+        c.total_units = (int32_t)p.total_units;
+        c.out_lo = (int32_t)sg.out_lo;
+        c.out_hi = (int32_t)sg.out_hi;
+        c.ng = (int32_t)e->ng;
+        c.vlo = (int32_t)std::max<int64_t>(0, -sg.glob0);
+        c.vhi = (int32_t)std::max<int64_t>(0, std::min(sg.in_rows, sg.field_h - sg.glob0));
+        c.birth = e->birth;
+        c.survive = e->survive;
+        HIP_TRY(gol::launch_probe_pass(c, e->rule, s));
+        a.moved = st.moved();
+        a.pass_probed = st.pass_probed();
+    }
 #if GOL_WAVE_LOG
     a.wlog = g_dev_wave_log;
 #endif
@@ -967,6 +1003,64 @@ gol_status gol_plan_model(uint64_t h, uint64_t w, const gol_config* cfg, int ran
     return GOL_OK;
 }
 
+// The plans gol_create would build for an h x w GLOBAL field on a device of `cus`
+// CUs with those occupancies, on the host alone (gol_plan_neighbours,
+// gol_plan_probe_tiles).
+static gol_status model_plans(gol_engine* e, uint64_t h, uint64_t w, const gol_config* cfg, int cus,
+                              int occ_classic, int occ_hand)
+{
+    e->model.on = true;
+    e->model.cus = cus;
+    e->model.occ_c = occ_classic;
+    e->model.occ_h = occ_hand;
+    e->R = h;
+    GOL_TRY(host_layout(e, h, w, cfg));
+    std::vector<std::vector<SegDesc>> raw;
+    GOL_TRY(raw_regions(e, h, cfg, nullptr, raw));
+    decide_passes(e, (size_t)(e->buf_rows + 2 * gol::kGuardRows) * e->stride);
+    GOL_TRY(build_plans(e, raw));
+    if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
+    return GOL_OK;
+}
+
+gol_status gol_plan_probe_tiles(uint64_t h, uint64_t w, const gol_config* cfg, int cus,
+                                int occ_classic, int occ_hand, uint32_t* table, uint64_t cap,
+                                uint32_t* tile_rows, uint32_t* tile_words, uint32_t* slots,
+                                uint64_t* ntile, uint64_t* ncol)
+{
+    if (!ntile || !ncol) return fail(GOL_EINVAL, "null out");
+    *ntile = *ncol = 0;
+    if (tile_rows) *tile_rows = (uint32_t)gol::kCopyTileRows;
+    if (tile_words) *tile_words = (uint32_t)gol::kCopyTileWords;
+    if (slots) *slots = (uint32_t)gol::kProbeSlots;
+    gol_status st = check_cfg(cfg);
+    if (st != GOL_OK) return st;
+    if (h == 0 || w == 0) return fail(GOL_EINVAL, "h and w must be >= 1");
+    if (h > (1ull << 40) || w > (1ull << 40)) return fail(GOL_EINVAL, "field too large");
+    if (cus <= 0 || occ_classic <= 0 || occ_hand < 0)
+        return fail(GOL_EINVAL, "cus and occ_classic must be >= 1, occ_hand >= 0");
+    if (cfg->semantics == GOL_SEM_TORUS) {  // the inner engine's plan (padded field)
+        TorusGeom tg;
+        GOL_TRY(torus_geometry(h, w, cfg, &tg));
+        gol_config ic = *cfg;
+        ic.semantics = GOL_SEM_GLOBAL;
+        ic.streams = 1;
+        ic.halo_depth = 0;
+        return gol_plan_probe_tiles(tg.ph, tg.pw, &ic, cus, occ_classic, occ_hand, table, cap,
+                                    tile_rows, tile_words, slots, ntile, ncol);
+    }
+    std::unique_ptr<gol_engine> e(new (std::nothrow) gol_engine());
+    if (!e) return fail(GOL_ENOMEM, "host allocation");
+    GOL_TRY(model_plans(e.get(), h, w, cfg, cus, occ_classic, occ_hand));
+    const auto& p = e->plans[0];
+    if (p.probe_tiles.empty() || p.nb_off.empty()) return GOL_OK;  // no pass
+    *ntile = p.probe_tiles.size() / gol::kProbeSlots;
+    *ncol = (uint64_t)p.copy_ncol;
+    if (table && cap >= p.probe_tiles.size())
+        std::memcpy(table, p.probe_tiles.data(), p.probe_tiles.size() * sizeof(uint32_t));
+    return GOL_OK;
+}
+
 gol_status gol_plan_neighbours(uint64_t h, uint64_t w, const gol_config* cfg, int cus,
                                int occ_classic, int occ_hand, int64_t* rects, uint32_t* offsets,
                                uint64_t unit_cap, uint32_t* ids, uint64_t id_cap, uint64_t* units,
@@ -992,17 +1086,7 @@ gol_status gol_plan_neighbours(uint64_t h, uint64_t w, const gol_config* cfg, in
     }
     std::unique_ptr<gol_engine> e(new (std::nothrow) gol_engine());
     if (!e) return fail(GOL_ENOMEM, "host allocation");
-    e->model.on = true;
-    e->model.cus = cus;
-    e->model.occ_c = occ_classic;
-    e->model.occ_h = occ_hand;
-    e->R = h;
-    GOL_TRY(host_layout(e.get(), h, w, cfg));
-    std::vector<std::vector<SegDesc>> raw;
-    GOL_TRY(raw_regions(e.get(), h, cfg, nullptr, raw));
-    decide_passes(e.get(), (size_t)(e->buf_rows + 2 * gol::kGuardRows) * e->stride);
-    GOL_TRY(build_plans(e.get(), raw));
-    if (e->plans.empty()) return fail(GOL_ESTATE, "no launch plan");
+    GOL_TRY(model_plans(e.get(), h, w, cfg, cus, occ_classic, occ_hand));
     const auto& p = e->plans[0];
     *units = (uint64_t)p.total_units;
     *nids = p.nb_ids.size();
@@ -1701,7 +1785,7 @@ static gol_status rect_bounds(const gol_engine* e, uint64_t y, uint64_t x, uint6
 // The activity counters of an engine, summed over its units (and over the parts
 // of a composite engine), after everything issued on its stream has run.
 struct ActTotals {
-    uint64_t computed = 0, skipped = 0, copied = 0, probed = 0, elided = 0;
+    uint64_t computed = 0, skipped = 0, copied = 0, probed = 0, elided = 0, pass_probed = 0;
 };
 static gol_status read_activity(gol_engine* e, ActTotals& t)
 {
@@ -1720,6 +1804,7 @@ static gol_status read_activity(gol_engine* e, ActTotals& t)
         t.copied += st.copied()[u];
         t.probed += st.probed()[u];
         t.elided += st.elided()[u];
+        t.pass_probed += st.pass_probed()[u];
     }
     // launches that every unit skipped at the one-load exit (only plan 0's
     // launches of a step ever skip)
@@ -1919,14 +2004,16 @@ gol_status gol_reset_timing(gol_engine* e)
         HIP_TRY(hipSetDevice(e->device));
         // Every counter: computed / skipped, copied and busy[0] lie one after the
         // other, the probed ones behind busy[1], the elided ones behind the pass's and
-        // the probe's flags.  The streaks, the flags and busy[1] are not
-        // statistics but the skip's own state within a step, which each step's
-        // first launch starts afresh: a reset leaves them alone.
+        // the probe's flags, the probe pass's behind its words.  The streaks, the
+        // flags, the words and busy[1] are not statistics but the skip's own state
+        // within a step, which each step's first launch starts afresh: a reset
+        // leaves them alone.
         const ActState as{e->d_streak, (size_t)e->act_units};
         HIP_TRY(hipMemsetAsync(as.act(), 0, (size_t)(as.busy() + 1 - as.act()) * sizeof(uint32_t),
                                e->stream));
         HIP_TRY(hipMemsetAsync(as.probed(), 0, as.units * sizeof(uint32_t), e->stream));
         HIP_TRY(hipMemsetAsync(as.elided(), 0, as.units * sizeof(uint32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(as.pass_probed(), 0, as.units * sizeof(uint32_t), e->stream));
     }
     return GOL_OK;
 }
@@ -1937,6 +2024,15 @@ gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units)
     ActTotals t;
     GOL_TRY(read_activity(e, t));
     if (probed_units) *probed_units = t.probed;
+    return GOL_OK;
+}
+
+gol_status gol_activity_pass_probed(gol_engine* e, uint64_t* pass_probed_units)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    ActTotals t;
+    GOL_TRY(read_activity(e, t));
+    if (pass_probed_units) *pass_probed_units = t.pass_probed;
     return GOL_OK;
 }
 

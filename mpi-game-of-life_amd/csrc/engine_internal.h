@@ -72,7 +72,12 @@ struct ActState {
     uint32_t* held() const { return base + 7 * units + 2; }
     // per unit: passes that found it calm with its rows already in the destination
     uint32_t* elided() const { return base + 8 * units + 2; }
-    size_t words() const { return 9 * units + 2; }
+    // per unit: the probe pass's word (life_probe.hip), zeroed before every pass: 1 =
+    // a tile that meets the unit's dilated rectangles changes in one generation
+    uint32_t* moved() const { return base + 9 * units + 2; }
+    // per unit: first launches that took it through on the probe pass's word
+    uint32_t* pass_probed() const { return base + 10 * units + 2; }
+    size_t words() const { return 11 * units + 2; }
 };
 
 // gol_create splits GLOBAL fields of at least this many rows into 2 same-device
@@ -322,6 +327,11 @@ struct gol_engine {
         std::vector<uint32_t> owners;
         uint32_t* d_own = nullptr;
         int32_t copy_ncol = 0;
+        // probe pass (life_probe.hip): per tile of the copy pass the units one of whose
+        // rectangles, dilated by K - 1 cells, meets it; kProbeSlots slots per tile.
+        // Empty: the plan takes no probe pass (its first launch probes in the kernel)
+        std::vector<uint32_t> probe_tiles;
+        uint32_t* d_ptab = nullptr;
         // a copy of an earlier plan of the same rows (rank engines: the full-depth
         // launches of a round share one plan); its device tables are the owner's
         bool alias = false;
@@ -375,6 +385,8 @@ struct gol_engine {
     bool probe_on = false;  // the still probe (GOL_DEV_STILL_PROBE=0 turns it off)
     bool elide_on = false;  // the copy pass leaves rows its destination already holds
                             // (GOL_DEV_COPY_ELIDE=0 turns it off)
+    bool ppass_on = false;  // the probe pass before a step's first launch
+                            // (GOL_DEV_PROBE_PASS=0 turns it off)
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on

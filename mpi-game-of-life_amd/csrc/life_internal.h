@@ -155,6 +155,14 @@ struct StepArgs {
     int32_t through;
     int32_t launch_idx;
     uint32_t* held;
+    // Probe pass (life_probe.hip; set with probe, or both null):
+    // life_probe_kernel, enqueued directly before this launch on the same stream, left
+    // moved[unit] = 0 exactly where no tile that meets the unit's rectangles dilated by
+    // depth - 1 differs after one generation, and stored those tiles' rows.  Such a
+    // unit takes the probe's quiet exit without a field load and counts in
+    // pass_probed[unit] as well; every other unit probes as without the pass.
+    const uint32_t* moved;
+    uint32_t* pass_probed;
 };
 constexpr uint32_t kStreakCap = 255;
 
@@ -265,6 +273,31 @@ struct CopyArgs {
     int32_t vlo, vhi;  // local rows inside the buffer and the field; others store 0
 };
 hipError_t launch_copy_pass(const CopyArgs& a, hipStream_t s);
+
+// The probe pass (life_probe.hip, DESIGN §4 "Probe pass"): one generation over the
+// copy pass's tiles before a step's first launch, in the copy pass's shape.  A device
+// table gives per tile the units one of whose rectangles, dilated by depth - 1
+// cells, meets it (kProbeSlots slots, unused ones ~0).  A tile whose cells all keep
+// their state stores its rows to `dst` as the copy pass would; any other tile stores
+// moved[unit] = 1 for its listed units and no row.  moved[] is zeroed on the stream
+// directly before the kernel.
+constexpr int kProbeSlots = 8;
+struct ProbeArgs {
+    const uint64_t* src;  // row 0 of the launch's pbuf[0] and pbuf[1]
+    uint64_t* dst;
+    const uint32_t* tiles;  // ntile x kProbeSlots unit indices
+    uint32_t* moved;        // total_units words
+    int64_t stride;    // words per buffer row
+    int64_t base_row;  // buffer row of the segment's local row 0
+    uint64_t lastmask; // stored-form valid bits of group ng - 1
+    int32_t ntile, ncol;
+    int32_t total_units;
+    int32_t out_lo, out_hi;  // the segment's output rows (local)
+    int32_t ng;
+    int32_t vlo, vhi;  // local rows inside the buffer and the field; others are dead
+    uint32_t birth, survive;
+};
+hipError_t launch_probe_pass(const ProbeArgs& a, RuleKind rule, hipStream_t s);
 
 // Resident 256-thread blocks per CU of the stencil kernel (occupancy query).
 // mp: of the multi-pass kernels (0 where none exists)

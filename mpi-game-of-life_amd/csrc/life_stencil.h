@@ -188,6 +188,21 @@ __device__ __forceinline__ Ends ends(const Pl<NP>& x)
     e.rn = __builtin_amdgcn_alignbit(ln, x.v[0], 1);        // (first >> 1) | (ln << 31)
     return e;
 }
+// The same with the wave shifts' zeros filled in (the probe pass's tiles,
+// life_probe.hip): lane 0 gives in `left` the last plane of the group left of its
+// own, lane 63 in `right` the first plane of the group right of its own; 0 in every
+// other lane.  (A form of its own, not `ends(x)` calling this one with zeros, so that
+// not one token of what the stencil kernel's steady loops compile from changes.)
+template <int NP>
+__device__ __forceinline__ Ends ends(const Pl<NP>& x, uint32_t left, uint32_t right)
+{
+    const uint32_t hp = lane_from_left(x.v[NP - 1]) | left;
+    const uint32_t ln = lane_from_right(x.v[0]) | right;
+    Ends e;
+    e.l0 = __builtin_amdgcn_alignbit(x.v[NP - 1], hp, 31);
+    e.rn = __builtin_amdgcn_alignbit(ln, x.v[0], 1);
+    return e;
+}
 template <int NP>
 __device__ __forceinline__ uint32_t left_of(const Pl<NP>& x, const Ends& e, int k)
 {
@@ -350,12 +365,12 @@ constexpr bool pair_rule(int RULE) { return GOL_PAIR_SUM && (RULE == RULE_REF ||
 // One stage step: ingest row r (x, generation g-1), emit row r-1 at generation g.
 // `pair`: the step reduces the pair (even ingested row; a constant once the
 // caller's loops are unrolled).
+// (stage_step_ends: with the row's horizontal end columns given, see `ends`)
 template <int RULE, int NP>
-__device__ __forceinline__ Pl<NP> stage_step(StageT<NP>& st, const Pl<NP>& x, uint32_t birth,
-                                             uint32_t survive, bool pair)
+__device__ __forceinline__ Pl<NP> stage_step_ends(StageT<NP>& st, const Pl<NP>& x, const Ends& e,
+                                                  uint32_t birth, uint32_t survive, bool pair)
 {
     constexpr bool kPairSum = pair_rule(RULE);
-    const Ends e = ends(x);
     Pl<NP> s3, c3, y;
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
@@ -388,6 +403,12 @@ __device__ __forceinline__ Pl<NP> stage_step(StageT<NP>& st, const Pl<NP>& x, ui
     st.cc = c3;
     st.al = x;
     return y;
+}
+template <int RULE, int NP>
+__device__ __forceinline__ Pl<NP> stage_step(StageT<NP>& st, const Pl<NP>& x, uint32_t birth,
+                                             uint32_t survive, bool pair)
+{
+    return stage_step_ends<RULE>(st, x, ends(x), birth, survive, pair);
 }
 
 // Steps per block (rows prefetched ahead through the register ring): 8 for the
@@ -874,6 +895,20 @@ void life_tb_kernel(StepArgs a)
                 return load_field<NP>(reinterpret_cast<const uint64_t*>(
                     in0 + (int64_t)min(t, T - 1) * row_bytes));
             };
+            // Probe pass (StepArgs::moved): a word of 0 says that no tile meeting the
+            // unit's dilated rectangles changes in one generation, which is this
+            // probe's condition and more, and that those tiles hold the unit's rows in
+            // the output buffer: the quiet exit below, with no field row loaded.
+            if (a.moved && __builtin_amdgcn_readfirstlane(a.moved[unit]) == 0u) {
+                if (lane == 0) {
+                    a.streak_out[unit] = min(streak + 1u, kStreakCap);
+                    if (a.act) a.act[2 * unit] += 1u;
+                    if (a.probed) a.probed[unit] += 1u;
+                    if (a.pass_probed) a.pass_probed[unit] += 1u;
+                    if (a.held) a.held[unit] = 1u;
+                }
+                return;
+            }
             StageT<NP> pst = {};
             Pl<NP> moved = {};  // OR of (generation 1) ^ (input) over the exact rows
             Grp<NP> g[kProbeRows];

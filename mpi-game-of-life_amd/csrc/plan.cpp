@@ -380,7 +380,9 @@ void free_plan(gol_engine::Plan& q)
     if (q.dpairs) (void)hipFree(q.dpairs);
     if (q.d_nb) (void)hipFree(q.d_nb);
     if (q.d_own) (void)hipFree(q.d_own);
+    if (q.d_ptab) (void)hipFree(q.d_ptab);
     q.d_own = nullptr;
+    q.d_ptab = nullptr;
     q.dev = nullptr;
     q.dpairs = nullptr;
     q.d_nb = nullptr;
@@ -491,35 +493,58 @@ void build_neighbours(gol_engine::Plan& p, int64_t ng, int K)
 // (tests/test_activity_neighbours.py), so every word of a tile has an owner among
 // them.  Left empty (no pass) where a tile has more owners than slots (row blocks of
 // a few rows) or the indices would not fit 32 bits.
-static void build_copy_owners(gol_engine::Plan& p, int64_t ng)
+// The probe pass's table (life_probe.hip) is the same table over the same tiles with
+// every rectangle dilated first, by `drows` rows and `dwords` lane groups on each
+// side, and clipped to the segment's output rows and the field's groups: a cell
+// within K - 1 <= 63 cells of groups [q0, q1) lies in groups [q0 - 1, q1].  Returns
+// the column segments per row chunk, 0 with `own` empty where there is no table.
+static int32_t build_tile_units(const gol_engine::Plan& p, int64_t ng, int64_t drows,
+                                int64_t dwords, int64_t S, std::vector<uint32_t>& own)
 {
-    p.owners.clear();
-    p.copy_ncol = 0;
+    own.clear();
     const int64_t lim = int64_t(1) << 27;
-    if (p.segs.size() != 1 || p.segs[0].out_hi >= 8 * lim || ng >= lim) return;
+    if (p.segs.size() != 1 || p.segs[0].out_hi >= 8 * lim || ng >= lim) return 0;
     const SegDesc& sg = p.segs[0];
-    const int64_t R = gol::kCopyTileRows, C = gol::kCopyTileWords, S = gol::kCopyOwners;
+    const int64_t R = gol::kCopyTileRows, C = gol::kCopyTileWords;
     const int64_t ncol = (ng + C - 1) / C, nrow = (std::max(sg.out_hi, sg.out_lo) - sg.out_lo + R - 1) / R;
-    if (ncol * nrow <= 0 || ncol * nrow >= lim) return;
+    if (ncol * nrow <= 0 || ncol * nrow >= lim) return 0;
     std::vector<URect> rc;
     unit_rects(p, ng, rc);
-    std::vector<uint32_t> own((size_t)(ncol * nrow * S), ~0u);
+    std::vector<uint32_t> tab((size_t)(ncol * nrow * S), ~0u);
     for (int64_t u = 0; u < p.total_units; ++u)
         for (int k = 0; k < 2; ++k) {
             const URect& r = rc[(size_t)(2 * u + k)];
             if (r.r1 <= r.r0 || r.q1 <= r.q0) continue;
-            if (r.r0 < sg.out_lo || r.r1 > sg.out_hi || r.q0 < 0 || r.q1 > ng) return;
-            for (int64_t i = (r.r0 - sg.out_lo) / R; i <= (r.r1 - 1 - sg.out_lo) / R; ++i)
-                for (int64_t c = r.q0 / C; c <= (r.q1 - 1) / C; ++c) {
-                    uint32_t* slot = &own[(size_t)((i * ncol + c) * S)];
+            if (r.r0 < sg.out_lo || r.r1 > sg.out_hi || r.q0 < 0 || r.q1 > ng) return 0;
+            const int64_t r0 = std::max(r.r0 - drows, sg.out_lo), r1 = std::min(r.r1 + drows, sg.out_hi);
+            const int64_t q0 = std::max<int64_t>(r.q0 - dwords, 0), q1 = std::min(r.q1 + dwords, ng);
+            for (int64_t i = (r0 - sg.out_lo) / R; i <= (r1 - 1 - sg.out_lo) / R; ++i)
+                for (int64_t c = q0 / C; c <= (q1 - 1) / C; ++c) {
+                    uint32_t* slot = &tab[(size_t)((i * ncol + c) * S)];
                     int64_t j = 0;
                     while (j < S && slot[j] != ~0u && slot[j] != (uint32_t)u) ++j;
-                    if (j == S) return;
+                    if (j == S) return 0;
                     slot[j] = (uint32_t)u;
                 }
         }
-    p.owners.swap(own);
-    p.copy_ncol = (int32_t)ncol;
+    own.swap(tab);
+    return (int32_t)ncol;
+}
+
+static void build_copy_owners(gol_engine::Plan& p, int64_t ng, int K)
+{
+    p.copy_ncol = build_tile_units(p, ng, 0, 0, gol::kCopyOwners, p.owners);
+    // the probe pass: only where the copy pass has its table (the same tiles), and
+    // K - 1 columns stay within one lane group
+    // build_tile_units clips to the segment's output rows, the pass's argument needs
+    // R(U) clipped to the field: only a segment whose output rows are the whole field
+    // (plan 0 of a single-GPU engine) gets the table
+    p.probe_tiles.clear();
+    if (p.segs.size() != 1) return;
+    const SegDesc& sg = p.segs[0];
+    const bool whole = sg.glob0 == 0 && sg.out_lo == 0 && sg.out_hi == sg.field_h;
+    if (p.copy_ncol > 0 && whole && K >= 1 && K - 1 <= 63)
+        build_tile_units(p, ng, K - 1, K > 1 ? 1 : 0, gol::kProbeSlots, p.probe_tiles);
 }
 
 gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& raw)
@@ -755,7 +780,7 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
                               !(p.hand && p.multi_blk) && p.total_units > 0 &&
                               p.total_units < (int64_t(1) << 28);
         if (act_plan) build_neighbours(p, (int64_t)e->ng, (int)e->K);
-        if (act_plan && e->planes == 2) build_copy_owners(p, (int64_t)e->ng);
+        if (act_plan && e->planes == 2) build_copy_owners(p, (int64_t)e->ng, (int)e->K);
         max_units = std::max(max_units, p.total_units);
         any_hand |= p.hand && p.multi_blk;
         any_mp |= p.npass > 1;
@@ -788,6 +813,11 @@ gol_status build_plans(gol_engine* e, const std::vector<std::vector<SegDesc>>& r
             HIP_TRY(hipMalloc(&p.d_own, sizeof(uint32_t) * p.owners.size()));
             HIP_TRY(hipMemcpy(p.d_own, p.owners.data(), sizeof(uint32_t) * p.owners.size(),
                               hipMemcpyHostToDevice));
+        }
+        if (p.d_own && !p.probe_tiles.empty()) {
+            HIP_TRY(hipMalloc(&p.d_ptab, sizeof(uint32_t) * p.probe_tiles.size()));
+            HIP_TRY(hipMemcpy(p.d_ptab, p.probe_tiles.data(),
+                              sizeof(uint32_t) * p.probe_tiles.size(), hipMemcpyHostToDevice));
         }
         return GOL_OK;
     };

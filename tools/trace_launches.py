@@ -4,7 +4,8 @@
 
 A step of 1000 generations at K = 16 is 62 depth-16 launches and a depth-8 remainder;
 with the copy pass (life_copy.hip) life_calm_kernel and life_copy_kernel precede
-launch 2 and the remainder.  Medians over the last `--steps` whole steps of: launch 1
+launch 2 and the remainder, and with the probe pass (life_probe.hip)
+life_probe_zero_kernel and life_probe_kernel precede launch 1.  Medians over the last `--steps` whole steps of: launch 1
 (the still probe), the pass and launch 2 (each, and from the pass's start to the
 launch's end),
 launch 3 (skips by its lists), launches 4-62 (the one-load exit; duration and pitch),
@@ -33,7 +34,8 @@ def main():
     ev = []
     for r in csv.DictReader(open(a.trace)):
         name = r["Kernel_Name"]
-        kind = "copy" if ("life_copy_kernel" in name or "life_calm_kernel" in name) else depth_of(name)
+        kind = ("copy" if ("life_copy_kernel" in name or "life_calm_kernel" in name)
+                else "probe" if "life_probe_" in name else depth_of(name))
         if kind is not None:
             ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), kind))
     ev.sort()
@@ -41,7 +43,7 @@ def main():
     steps, cur = [], []
     for s, e, kind in ev:
         cur.append((s, e, kind))
-        if kind != "copy" and kind != a.depth:
+        if kind not in ("copy", "probe") and kind != a.depth:
             steps.append(cur)
             cur = []
     full = [st for st in steps if sum(1 for x in st if x[2] == a.depth) >= 4][-a.steps:]
@@ -55,6 +57,11 @@ def main():
         rem = st[-1]
         copies = [x for x in st if x[2] == "copy"]
         add("launch1_us", deep[0][1] - deep[0][0])
+        pp = [x for x in st if x[2] == "probe" and x[0] <= deep[0][0]]
+        if pp:
+            add("probe_pass_us", pp[-1][1] - pp[0][0])
+            add("probe_pass_tile_kernel_us", pp[-1][1] - pp[-1][0])
+        add("launch1_with_pass_us", deep[0][1] - (pp[0][0] if pp else deep[0][0]))
         add("launch2_us", deep[1][1] - deep[1][0])
         add("launch3_us", deep[2][1] - deep[2][0])
         for x, y in zip(deep[3:], deep[4:]):
@@ -69,7 +76,7 @@ def main():
         if pr:
             add("pass_remainder_us", pr[-1][1] - pr[0][0])
         add("remainder_with_pass_us", rem[1] - (pr[0][0] if pr else rem[0]))
-        add("step_span_us", rem[1] - deep[0][0])
+        add("step_span_us", rem[1] - (pp[0][0] if pp else deep[0][0]))
     out = {"steps": len(full), "launches_per_step": statistics.median(len(st) for st in full)}
     out.update({k: round(statistics.median(v), 2) for k, v in cols.items()})
     print(json.dumps(out, indent=1))
