@@ -266,6 +266,16 @@ gol_status gol_activity_elided(gol_engine* e, uint64_t* elided_units);
  * runs wherever the copy pass does, and GOL_DEV_PROBE_PASS=0 at create turns it off
  * (the count stays 0). */
 gol_status gol_activity_pass_probed(gol_engine* e, uint64_t* pass_probed_units);
+/* Rows both buffers hold: a tile of the probe pass that keeps its state stores no row
+ * where the buffer it would write holds those rows already, word for word.  The last
+ * launch of the step before records that per unit (a unit that did not compute in it),
+ * and every other writer of the field -- a load, gol_init_random, gol_write_rect, a
+ * torus round's wrap, a timed or hand-off launch -- withdraws the record.
+ * gol_activity_pass_kept returns how many tile passes left their rows that way since
+ * create or gol_reset_timing.  No field word and no other counter depends on it;
+ * GOL_DEV_TWIN=0 at create turns it off (every such tile stores; the count stays 0).
+ * Torus engines wrap before every round: their count stays 0. */
+gol_status gol_activity_pass_kept(gol_engine* e, uint64_t* kept_tiles);
 
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */

@@ -40,7 +40,7 @@ EXPORTS = [
     "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
     "gol_activity_copied", "gol_activity_probed", "gol_activity_elided", "gol_torus_geometry", "gol_torus_pad",
-    "gol_activity_pass_probed", "gol_plan_probe_tiles",
+    "gol_activity_pass_probed", "gol_plan_probe_tiles", "gol_activity_pass_kept",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
 ]
 
@@ -204,6 +204,7 @@ def lib():
     L.gol_activity_probed.argtypes = [vp, pu64]
     L.gol_activity_elided.argtypes = [vp, pu64]
     L.gol_activity_pass_probed.argtypes = [vp, pu64]
+    L.gol_activity_pass_kept.argtypes = [vp, pu64]
     L.gol_plan_probe_tiles.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, u64,
                                        ctypes.POINTER(u32), ctypes.POINTER(u32),
                                        ctypes.POINTER(u32), pu64, pu64]
@@ -228,7 +229,8 @@ def lib():
                  "gol_digest_rows", "gol_comm_info", "gol_plan_model", "gol_plan_passes",
                  "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity",
                  "gol_plan_neighbours", "gol_activity_copied", "gol_activity_probed",
-                 "gol_activity_elided", "gol_activity_pass_probed", "gol_plan_probe_tiles"]:
+                 "gol_activity_elided", "gol_activity_pass_probed", "gol_plan_probe_tiles",
+                 "gol_activity_pass_kept"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -596,6 +598,13 @@ class Engine:
         word, without a field load in the launch (gol_activity_pass_probed)."""
         c = ctypes.c_uint64()
         _check(lib().gol_activity_pass_probed(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_pass_kept(self):
+        """Tile passes of the probe pass that stored no row because the other buffer
+        already held the tile's rows (gol_activity_pass_kept)."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_pass_kept(self._h, ctypes.byref(c)))
         return c.value
 
     def activity_elided(self):

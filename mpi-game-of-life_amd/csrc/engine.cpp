@@ -311,6 +311,24 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
         // of its own before it (GOL_DEV_PROBE_PASS=0 = off: the in-kernel probe alone)
         const char* pp = std::getenv("GOL_DEV_PROBE_PASS");
         e->ppass_on = e->probe_on && !(pp && std::atoi(pp) == 0);
+        // rows both buffers hold: the probe pass stores no tile whose rows the other
+        // buffer holds already, on the word of the copy pass's calm kernel before the
+        // last launch of the step before (GOL_DEV_TWIN=0 = off: every tile without a
+        // difference stores, as in r12).  One counter word per tile of the pass.
+        const char* tw = std::getenv("GOL_DEV_TWIN");
+        e->twin_on = e->ppass_on && e->pass_on && !(tw && std::atoi(tw) == 0);  // (act_on: a plan)
+        if (e->twin_on) {
+            const auto& p0 = e->plans[0];
+            e->twin_on = p0.d_own && p0.d_ptab && e->planes == 2 &&
+                         p0.owners.size() / gol::kCopyOwners ==
+                             p0.probe_tiles.size() / gol::kProbeSlots;
+        }
+        if (e->twin_on) {
+            const auto& p0 = e->plans[0];
+            e->kept_tiles = (int64_t)(p0.owners.size() / gol::kCopyOwners);
+            HIP_TRY(hipMalloc(&e->d_kept, (size_t)e->kept_tiles * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(e->d_kept, 0, (size_t)e->kept_tiles * sizeof(uint32_t), e->stream));
+        }
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return GOL_OK;
@@ -640,6 +658,12 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     // copy elision: the pass may take ActState::held (case P) / every calm unit's
     // rows are in the output buffer already (case R)
     bool pass_held = false, pass_all = false;
+    // Rows both buffers hold: a launch of plan 0 writes the field, so it
+    // clears twin_ok unless it is a launch of an activity step, whose last launch
+    // decides: twin_last = that launch, reading history, so that the calm kernel can
+    // write twin[] before it; if none does, the flag goes.
+    bool twin_drop = e->twin_on && e->d_streak && plan == 0;
+    bool twin_last = false, twin_set = false;
     if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
         const ActState st{e->d_streak, (size_t)e->act_units};
         a.act = st.act();
@@ -666,6 +690,8 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             // the step's second launch: its streaks are 0 or 1, no unit can skip
             pass = a.through && e->act_launch == 1;
             pass_held = e->act_probed;
+            twin_drop = e->twin_on && e->act_last;
+            twin_last = twin_drop && !a.no_hist;
         } else if (may && depth < e->K && e->act_hist >= 0 && e->through_on >= 2) {
             a.streak_in = st.streak(e->act_hist);
             a.nb_off = p.d_nb;
@@ -679,6 +705,7 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             // launch before
             pass_all = e->act_rem > 0;
             ++e->act_rem;
+            twin_last = twin_drop = e->twin_on && e->act_last;
         } else {
             e->act_hist = -1;
             e->act_probed = false;
@@ -723,8 +750,28 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         c.ng = (int32_t)e->ng;
         c.vlo = (int32_t)std::max<int64_t>(0, -sg.glob0);
         c.vhi = (int32_t)std::max<int64_t>(0, std::min(sg.in_rows, sg.field_h - sg.glob0));
+        // the step's last launch: the calm kernel writes twin[] as well
+        if (twin_last) {
+            c.twin = st.twin();
+            c.twin_ok = st.twin_ok();
+            twin_set = true;
+        }
         HIP_TRY(gol::launch_copy_pass(c, s));
         a.through = 2;
+    }
+    // ... and where that launch takes no copy pass (a depth-K launch after the step's
+    // second), the calm kernel runs for twin[] alone, on the streaks the launch reads
+    if (twin_last && !twin_set && a.streak_in && a.nb_off && !a.no_hist) {
+        const ActState st{e->d_streak, (size_t)e->act_units};
+        gol::CopyArgs c{};
+        c.streak_in = a.streak_in;
+        c.nb_off = a.nb_off;
+        c.nb_ids = a.nb_ids;
+        c.total_units = (int32_t)p.total_units;
+        c.twin = st.twin();
+        c.twin_ok = st.twin_ok();
+        HIP_TRY(gol::launch_twin_flags(c, s));
+        twin_set = true;
     }
     // Probe pass (life_probe.hip): before a step's first launch, where that
     // launch probes, under the copy pass's conditions.  The launch has no history, so
@@ -754,10 +801,25 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         c.vhi = (int32_t)std::max<int64_t>(0, std::min(sg.in_rows, sg.field_h - sg.glob0));
         c.birth = e->birth;
         c.survive = e->survive;
+        // rows both buffers hold: the copy pass's owners, over the same tile grid
+        if (e->twin_on && p.d_own && e->d_kept) {
+            if (p.owners.size() / gol::kCopyOwners != (size_t)c.ntile ||
+                e->kept_tiles != (int64_t)c.ntile || p.copy_ncol != c.ncol)
+                return fail(GOL_ESTATE, "probe pass and copy pass over different tiles");
+            c.owners = p.d_own;
+            c.twin = st.twin();
+            c.twin_ok = st.twin_ok();
+            c.kept = e->d_kept;
+        }
         HIP_TRY(gol::launch_probe_pass(c, e->rule, s));
         a.moved = st.moved();
         a.pass_probed = st.pass_probed();
     }
+    // the step's only launch, which probes and writes held[] for every unit: twin[] is
+    // held[], copied behind the launch
+    const bool twin_held = twin_drop && !twin_set && a.no_hist && a.probe && a.held;
+    // after the probe pass, which reads the flag as the step before left it
+    if (twin_drop && !twin_set && !twin_held) GOL_TRY(twin_clear(e, s));
 #if GOL_WAVE_LOG
     a.wlog = g_dev_wave_log;
 #endif
@@ -784,6 +846,10 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         for (const auto& sg : p.segs) rows += (double)std::max<int64_t>(0, sg.out_hi - sg.out_lo);
         GOL_TRY(timing_end(e, s, e0, e1, p.own_rows * (double)e->W * depth * passes,
                            (comp * p.groups + comp_half) * cols * passes, rows * passes));
+    }
+    if (twin_held) {
+        const ActState st{e->d_streak, (size_t)e->act_units};
+        HIP_TRY(gol::launch_twin_held(a.held, st.twin(), st.twin_ok(), (int32_t)p.total_units, s));
     }
     if (swap) e->cur = (e->cur + passes) % e->nbuf;
     return GOL_OK;
@@ -817,6 +883,14 @@ gol_status quiesce(gol_engine* e)
     for (gol_engine* n : {e->up, e->down})
         if (n && n->comm_stream) HIP_TRY(hipStreamSynchronize(n->comm_stream));
     e->halo_fresh = false;
+    return GOL_OK;
+}
+
+gol_status twin_clear(gol_engine* e, hipStream_t s)
+{
+    if (!e->d_streak || !e->twin_on) return GOL_OK;  // nobody reads the flag
+    const ActState st{e->d_streak, (size_t)e->act_units};
+    HIP_TRY(hipMemsetAsync(st.twin_ok(), 0, sizeof(uint32_t), s ? s : e->stream));
     return GOL_OK;
 }
 
@@ -1154,6 +1228,7 @@ void gol_destroy(gol_engine* e)
     }
     if (e->mpflags) (void)hipFree(e->mpflags);
     if (e->d_streak) (void)hipFree(e->d_streak);
+    if (e->d_kept) (void)hipFree(e->d_kept);
     if (e->d_err) (void)hipFree(e->d_err);
     if (e->res.flags) (void)hipFree(e->res.flags);
     for (hipEvent_t ev : {e->res.ev_in, e->res.ev_out})
@@ -1198,6 +1273,7 @@ static uint64_t load_rows_needed(const gol_engine* e)
 static gol_status upload(gol_engine* e, const uint64_t* words, uint64_t rs)
 {
     GOL_TRY(quiesce(e));
+    GOL_TRY(twin_clear(e));
     // clear everything (halos, unused rows) then copy each region, masking pad bits
     const size_t words_all = (size_t)(e->buf_rows + 2 * gol::kGuardRows) * e->stride;
     HIP_TRY(hipMemsetAsync(e->alloc[e->cur], 0, words_all * 8, e->stream));
@@ -1299,6 +1375,7 @@ gol_status gol_load_ascii(gol_engine* e, const char* buf, size_t len)
                                     std::to_string(len));
     // raw bytes to the device, packed there by the ASCII codec kernel
     GOL_TRY(quiesce(e));
+    GOL_TRY(twin_clear(e));
     DeviceBytes bytes;
     HIP_TRY(hipMalloc(&bytes.p, len));
     HIP_TRY(hipMemcpyAsync(bytes.p, buf, len, hipMemcpyHostToDevice, e->stream));
@@ -1384,6 +1461,7 @@ gol_status gol_init_random(gol_engine* e, uint64_t seed)
         return GOL_OK;
     }
     GOL_TRY(quiesce(e));
+    GOL_TRY(twin_clear(e));
     const size_t words_all = (size_t)(e->buf_rows + 2 * gol::kGuardRows) * e->stride;
     HIP_TRY(hipMemsetAsync(e->alloc[e->cur], 0, words_all * 8, e->stream));
     for (const auto& r : e->load_regions)
@@ -1422,11 +1500,15 @@ gol_status step_single(gol_engine* e, uint64_t generations)
     e->act_hist = -1;
     e->act_probed = false;
     e->act_rem = 0;
+    e->act_last = false;
     const gol_status st = step_single_launches(e, generations);
     e->act_launch = -1;
     e->act_hist = -1;
     e->act_probed = false;
     e->act_rem = 0;
+    e->act_last = false;
+    // a step that failed half-way leaves no statement about the buffers
+    if (st != GOL_OK) (void)twin_clear(e);
     return st;
 }
 
@@ -1453,6 +1535,7 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
             while (left > 0 && st == GOL_OK) {
                 const uint32_t d = pick_depth(e->K, left);
                 const int np = passes_for(e, 0, d, left);
+                e->act_last = left == (uint64_t)d * np;
                 st = launch(e, 0, d, true, nullptr, np);
                 left -= (uint64_t)d * np;
             }
@@ -1484,6 +1567,7 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
     while (left > 0) {
         const uint32_t d = pick_depth(e->K, left);
         const int np = passes_for(e, 0, d, left);
+        e->act_last = left == (uint64_t)d * np;
         GOL_TRY(launch(e, 0, d, true, nullptr, np));
         left -= (uint64_t)d * np;
     }
@@ -1681,6 +1765,7 @@ gol_status leaf_write(gol_engine* e, const std::vector<Region>& regs, uint64_t w
     // as a load: every stream of the engine finished, and the next step of a stripe
     // engine exchanges halos first (whether or not the rectangle meets its rows)
     GOL_TRY(quiesce(e));
+    GOL_TRY(twin_clear(e));
     std::vector<uint64_t> tmp;
     for (size_t k = 0; k < npc; ++k) {
         const RectPiece& p = pcs[k];
@@ -1786,6 +1871,7 @@ static gol_status rect_bounds(const gol_engine* e, uint64_t y, uint64_t x, uint6
 // of a composite engine), after everything issued on its stream has run.
 struct ActTotals {
     uint64_t computed = 0, skipped = 0, copied = 0, probed = 0, elided = 0, pass_probed = 0;
+    uint64_t pass_kept = 0;  // probe-pass tiles that left their rows (gol_engine::d_kept)
 };
 static gol_status read_activity(gol_engine* e, ActTotals& t)
 {
@@ -1809,6 +1895,11 @@ static gol_status read_activity(gol_engine* e, ActTotals& t)
     // launches that every unit skipped at the one-load exit (only plan 0's
     // launches of a step ever skip)
     if (!e->plans.empty()) t.skipped += (uint64_t)st.busy()[0] * (uint64_t)e->plans[0].total_units;
+    if (e->d_kept && e->kept_tiles > 0) {
+        std::vector<uint32_t> kept((size_t)e->kept_tiles);
+        HIP_TRY(hipMemcpy(kept.data(), e->d_kept, kept.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t k : kept) t.pass_kept += k;
+    }
     return GOL_OK;
 }
 
@@ -2014,6 +2105,9 @@ gol_status gol_reset_timing(gol_engine* e)
         HIP_TRY(hipMemsetAsync(as.probed(), 0, as.units * sizeof(uint32_t), e->stream));
         HIP_TRY(hipMemsetAsync(as.elided(), 0, as.units * sizeof(uint32_t), e->stream));
         HIP_TRY(hipMemsetAsync(as.pass_probed(), 0, as.units * sizeof(uint32_t), e->stream));
+        // (twin[] and twin_ok are state across steps, not statistics: left alone too)
+        if (e->d_kept)
+            HIP_TRY(hipMemsetAsync(e->d_kept, 0, (size_t)e->kept_tiles * sizeof(uint32_t), e->stream));
     }
     return GOL_OK;
 }
@@ -2033,6 +2127,15 @@ gol_status gol_activity_pass_probed(gol_engine* e, uint64_t* pass_probed_units)
     ActTotals t;
     GOL_TRY(read_activity(e, t));
     if (pass_probed_units) *pass_probed_units = t.pass_probed;
+    return GOL_OK;
+}
+
+gol_status gol_activity_pass_kept(gol_engine* e, uint64_t* kept_tiles)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    ActTotals t;
+    GOL_TRY(read_activity(e, t));
+    if (kept_tiles) *kept_tiles = t.pass_kept;
     return GOL_OK;
 }
 

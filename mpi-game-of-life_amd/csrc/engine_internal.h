@@ -77,7 +77,13 @@ struct ActState {
     uint32_t* moved() const { return base + 9 * units + 2; }
     // per unit: first launches that took it through on the probe pass's word
     uint32_t* pass_probed() const { return base + 10 * units + 2; }
-    size_t words() const { return 11 * units + 2; }
+    // per unit: 1 = both field buffers hold the unit's rows, word for word, as the
+    // step's last launch left them (life_copy.hip writes it, life_probe.hip reads it in
+    // the next step); it says so only while *twin_ok is 1, which every other writer
+    // of the field clears (DESIGN §4 "Probe pass: rows both buffers hold")
+    uint32_t* twin() const { return base + 11 * units + 2; }
+    uint32_t* twin_ok() const { return base + 12 * units + 2; }
+    size_t words() const { return 12 * units + 3; }
 };
 
 // gol_create splits GLOBAL fields of at least this many rows into 2 same-device
@@ -375,6 +381,9 @@ struct gol_engine {
     // remainder launches of the step issued so far (copy elision)
     bool act_probed = false;
     int act_rem = 0;
+    // the launch being issued is the step's last one (step_single_launches sets it):
+    // the one that decides ActState::twin
+    bool act_last = false;
     // what the engine may do, decided at create:
     bool act_on = false;    // skip units at all
     int through_on = 0;     // copy-through: 0 = off, 1 = launches at depth K, 2 = the
@@ -387,6 +396,11 @@ struct gol_engine {
                             // (GOL_DEV_COPY_ELIDE=0 turns it off)
     bool ppass_on = false;  // the probe pass before a step's first launch
                             // (GOL_DEV_PROBE_PASS=0 turns it off)
+    bool twin_on = false;   // the probe pass leaves rows that both buffers hold
+                            // (GOL_DEV_TWIN=0 turns it off)
+    // per tile of plan 0's probe pass: passes that left the tile's rows unstored
+    uint32_t* d_kept = nullptr;
+    int64_t kept_tiles = 0;
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on
@@ -465,6 +479,10 @@ gol_status get_event(gol_engine* e, hipEvent_t* ev);
 gol_status join_side_streams(gol_engine* e);
 gol_status quiesce(gol_engine* e);
 gol_status check_err(gol_engine* e);
+// Every writer of a field buffer other than an activity step's own launches calls
+// this: ActState::twin says nothing about the buffers from here on (a 4-byte memset
+// on the engine's stream, a memset node inside a captured step).
+gol_status twin_clear(gol_engine* e, hipStream_t s = nullptr);
 
 // Region I/O (gol_read_rect / gol_write_rect / gol_density).  A piece is a
 // non-wrapping rectangle in a leaf engine's field coordinates -- rows [frow, frow +

@@ -53,11 +53,32 @@ __global__ __launch_bounds__(256) void life_calm_kernel(CopyArgs a)
     bool still;
     const bool calm = unit_calm(a, unit, lane, &still);
     if (lane == 0) {
+        // Rows both buffers hold: before a step's last launch.  A calm unit's
+        // output rows equal its input rows, however they get there, and the launch's
+        // input buffer is the other one once the step has ended.  A unit that computes
+        // gets 0, quiet or not.
+        if (a.twin) {
+            a.twin[unit] = calm ? 1u : 0u;
+            if (unit == 0) *a.twin_ok = 1u;
+        }
+        if (!a.need) return;
         const bool holds =
             a.elided && (a.all_held || still || (a.held && a.held[unit] != 0u));
         a.need[unit] = (calm && !holds) ? 1u : 0u;
         if (calm && holds) a.elided[unit] += 1u;
     }
+}
+
+// twin[] after a step whose only launch probed: a unit that took the still
+// probe's quiet exit left its output rows equal to its input rows (copy elision's
+// case P reads the same flag for the same reason); every other unit computed.
+__global__ __launch_bounds__(256) void life_twin_held_kernel(const uint32_t* held, uint32_t* twin,
+                                                             uint32_t* twin_ok, int32_t units)
+{
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= (uint32_t)units) return;
+    twin[u] = held[u] != 0u ? 1u : 0u;
+    if (u == 0) *twin_ok = 1u;
 }
 
 // One wavefront per tile of kCopyTileRows rows x kCopyTileWords words, lane l = word
@@ -120,6 +141,23 @@ hipError_t launch_copy_pass(const CopyArgs& a, hipStream_t s)
     if (a.all_held && a.elided) return hipGetLastError();
     const unsigned blocks = ((unsigned)a.ntile + kWavesPerBlock - 1) / kWavesPerBlock;
     hipLaunchKernelGGL(life_copy_kernel, dim3(blocks), dim3(64 * kWavesPerBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_twin_held(const uint32_t* held, uint32_t* twin, uint32_t* twin_ok, int32_t units,
+                            hipStream_t s)
+{
+    if (units <= 0 || !held || !twin || !twin_ok) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(life_twin_held_kernel, dim3(((unsigned)units + 255) / 256), dim3(256), 0, s,
+                       held, twin, twin_ok, units);
+    return hipGetLastError();
+}
+
+hipError_t launch_twin_flags(const CopyArgs& a, hipStream_t s)
+{
+    if (a.total_units <= 0 || !a.twin || !a.twin_ok || a.need || a.elided) return hipErrorInvalidValue;
+    const unsigned ublocks = ((unsigned)a.total_units + kWavesPerBlock - 1) / kWavesPerBlock;
+    hipLaunchKernelGGL(life_calm_kernel, dim3(ublocks), dim3(64 * kWavesPerBlock), 0, s, a);
     return hipGetLastError();
 }
 

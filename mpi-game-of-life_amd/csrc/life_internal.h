@@ -271,8 +271,20 @@ struct CopyArgs {
     int32_t out_lo, out_hi;  // the segment's output rows (local)
     int32_t ng;
     int32_t vlo, vhi;  // local rows inside the buffer and the field; others store 0
+    // Rows both buffers hold (both set before a step's last launch, or both
+    // null): the first kernel also writes twin[unit] = calm, and *twin_ok = 1.  With
+    // `need` null it writes nothing else (launch_twin_flags).
+    uint32_t* twin;
+    uint32_t* twin_ok;
 };
 hipError_t launch_copy_pass(const CopyArgs& a, hipStream_t s);
+// The pass's first kernel alone, for twin[] only (need and elided null): before a
+// step's last launch where that is a depth-K launch that takes no copy pass.
+hipError_t launch_twin_flags(const CopyArgs& a, hipStream_t s);
+// twin[] = held[] (StepArgs::held) and *twin_ok = 1: after a step's only launch, where
+// that launch probed and wrote held[] for every unit.
+hipError_t launch_twin_held(const uint32_t* held, uint32_t* twin, uint32_t* twin_ok, int32_t units,
+                            hipStream_t s);
 
 // The probe pass (life_probe.hip, DESIGN §4 "Probe pass"): one generation over the
 // copy pass's tiles before a step's first launch, in the copy pass's shape.  A device
@@ -296,6 +308,14 @@ struct ProbeArgs {
     int32_t ng;
     int32_t vlo, vhi;  // local rows inside the buffer and the field; others are dead
     uint32_t birth, survive;
+    // Rows both buffers hold (all four set, or all null): a tile without a
+    // difference stores no row and counts in kept[tile] where *twin_ok is set, the
+    // tile has an owner (the copy pass's table, kCopyOwners slots per tile of the same
+    // grid) and twin[] is set for every owner: dst holds those rows already.
+    const uint32_t* owners;
+    const uint32_t* twin;
+    const uint32_t* twin_ok;
+    uint32_t* kept;  // ntile words
 };
 hipError_t launch_probe_pass(const ProbeArgs& a, RuleKind rule, hipStream_t s);
 

@@ -14,6 +14,12 @@
 // unit is listed for it and never marked), so it stored its rows, the unit's among
 // them, in the form the probe's quiet exit stores.  Every other unit probes in the
 // launch as it does without the pass and stores its whole rectangle afterwards.
+//
+// Rows both buffers hold: a tile without a difference leaves its
+// stores out where the destination holds its rows already, which the last launch of
+// the step before recorded per unit (ActState::twin, valid while twin_ok is set).
+// "Stored its rows" above then reads "the destination holds its rows": the same
+// content, so everything that follows from it stands.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,12 +64,25 @@ __global__ __launch_bounds__(256, RULE == RULE_GENERIC ? 1 : 8) void life_probe_
     uint32_t unit = ~0u;
     if (lane < kProbeSlots) unit = a.tiles[(size_t)tile * kProbeSlots + lane];
     const bool listed = unit < (uint32_t)a.total_units;
+    // Rows both buffers hold: the tile's owners (one per lane below
+    // kCopyOwners) and their words, loaded beside the listed units' so that the two
+    // chains of two loads run together.  twin_tile: dst holds every row of the tile.
+    // Such a tile does not take the exit below, so that whether it counts in kept[]
+    // does not hang on the order in which other tiles mark its units; it is a tile of
+    // still units beside units in motion, and the exit catches few tiles anyway.
+    uint32_t owner = ~0u;
+    if (a.twin && lane < kCopyOwners) owner = a.owners[(size_t)tile * kCopyOwners + lane];
+    const bool owned = owner < (uint32_t)a.total_units;
+    const uint32_t tw = owned ? a.twin[owner] : 1u;
+    const uint32_t tw_ok = a.twin ? *a.twin_ok : 0u;
+    const bool twin_tile = tw_ok != 0u && __builtin_amdgcn_ballot_w64(owned) != 0 &&
+                           __builtin_amdgcn_ballot_w64(tw == 0u) == 0;
     {
         const uint32_t m = listed ? __hip_atomic_load(a.moved + unit, __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_AGENT)
                                   : 1u;
         const bool any = __builtin_amdgcn_ballot_w64(listed) != 0;
-        if (any && __builtin_amdgcn_ballot_w64(m == 0u) == 0) return;
+        if (any && !twin_tile && __builtin_amdgcn_ballot_w64(m == 0u) == 0) return;
     }
     const int32_t q0 = (int32_t)seg * kCopyTileWords;
     const int32_t q = q0 + lane;
@@ -124,6 +143,13 @@ __global__ __launch_bounds__(256, RULE == RULE_GENERIC ? 1 : 8) void life_probe_
     if (__builtin_amdgcn_ballot_w64(diff != 0u) != 0) {
         // plain vector stores of one value by every writer, as busy[1]: no atomics
         if (listed) a.moved[unit] = 1u;
+        return;
+    }
+    // Every word of the tile belongs to one of its owners (their rectangles tile the
+    // field), and dst holds every owner's rows as the stores below would write them:
+    // nothing to store.  One wavefront per tile: a plain add by one lane.
+    if (twin_tile) {
+        if (lane == 0) a.kept[tile] += 1u;
         return;
     }
     if (!qin) return;

@@ -136,6 +136,7 @@ static uint64_t* interior(const gol_engine* e)
 static gol_status clear_current(gol_engine* in)
 {
     GOL_TRY(quiesce(in));
+    GOL_TRY(twin_clear(in));
     const size_t words_all = (size_t)(in->buf_rows + 2 * gol::kGuardRows) * in->stride;
     HIP_TRY(hipMemsetAsync(in->alloc[in->cur], 0, words_all * 8, in->stream));
     return GOL_OK;
@@ -147,6 +148,8 @@ gol_status torus_step(gol_engine* e, uint64_t generations)
     HIP_TRY(hipSetDevice(in->device));
     for (uint64_t left = generations; left > 0;) {
         const uint64_t g = std::min<uint64_t>(left, e->tG);
+        // (the wrap writes ghost cells of the current buffer alone)
+        GOL_TRY(twin_clear(in));
         HIP_TRY(gol::launch_torus_wrap(in->buf[in->cur], (int64_t)in->stride, (int64_t)e->H,
                                        (int64_t)e->W, (int64_t)e->tG, (int64_t)e->tGx, in->stream));
         GOL_TRY(gol_step(in, g));
