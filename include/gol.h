@@ -410,6 +410,70 @@ gol_status gol_rect_blit(const uint64_t* src, uint64_t src_stride_words, uint64_
                          uint64_t* dst, uint64_t dst_stride_words, uint64_t dx, uint64_t rows,
                          uint64_t cols, uint32_t op);
 
+/* ---- Snapshots: one earlier generation kept on the device ----
+ * One snapshot slot per engine: keep the field as it is now, ask later whether the
+ * field equals it or in how many cells it differs, go back to it, and step until the
+ * field repeats.  Nothing but one word or one count moves to the host.  An engine that
+ * never calls gol_snapshot allocates nothing for the slot.
+ * Engines: gol_create with GOL_SEM_GLOBAL (a composite engine keeps one slot per
+ * stripe and adds the stripes' answers up) or GOL_SEM_TORUS (the h x w interior is what
+ * is compared; the ghost cells are not).  GOL_SEM_REF_STRIPES engines, rank engines
+ * and group members return GOL_ESTATE from every call of this section: a partitioned
+ * field's answer is a collective one. */
+
+/* Keeps a device copy of the field as it is now, enqueued behind the engine's work; it
+ * does not wait on the host.  The first call allocates the slot (as much device memory
+ * as one of the engine's two field buffers; GOL_ENOMEM if that fails), a later call
+ * replaces the snapshot.  Loads, steps and edits after the call do not touch it. */
+gol_status gol_snapshot(gol_engine* e);
+/* *same = 1 if every cell of the h x w field equals the snapshot's, else 0.  Waits for
+ * the engine's work and reads both fields at most once: it may stop as soon as one
+ * difference is known.  GOL_ESTATE without a snapshot. */
+gol_status gol_snapshot_same(gol_engine* e, uint32_t* same);
+/* *cells = the exact number of field cells that differ from the snapshot's.  Waits for
+ * the engine's work.  GOL_ESTATE without a snapshot. */
+gol_status gol_snapshot_diff(gol_engine* e, uint64_t* cells);
+/* Makes the field the snapshot's field again; the snapshot stays.  A writer of the
+ * field like gol_write_rect: it finishes the engine's streams first.  GOL_ESTATE
+ * without a snapshot. */
+gol_status gol_snapshot_restore(gol_engine* e);
+/* Frees the slot (GOL_OK when there is none); gol_destroy does the same. */
+gol_status gol_snapshot_drop(gol_engine* e);
+
+/* Steps until the field repeats with a period that divides `lag`, or for
+ * max_generations.  This call uses the snapshot slot: it replaces whatever the slot
+ * held, and on return the slot holds what the last check left in it.
+ * 1 <= lag <= 65536; check_every = 0 means the least multiple of 64 that is >= lag,
+ * else check_every >= lag (GOL_EINVAL otherwise).  Checks happen at the generations
+ * g = c * check_every, c = 1, 2, ..., counted from the call: the field of generation
+ * g - lag is kept as the snapshot and compared with generation g's.  The first g at
+ * which they are equal ends the run: then the minimal period p (a divisor of lag) is
+ * found by stepping on through lag's proper divisors in ascending order, comparing
+ * each time, and the field of generation g is restored.  If the next check would lie
+ * beyond max_generations, the generations that remain are run and period = 0.
+ * On return the engine holds generation `advanced`'s field; with GOL_UNTIL_FINISH and a
+ * period found it then runs (max_generations - g) mod p generations more, after which
+ * it holds the field gol_step(e, max_generations) would have left.
+ * out->struct_size must be sizeof(gol_until) and flags 0 or GOL_UNTIL_FINISH
+ * (GOL_EINVAL otherwise, before anything is stepped).
+ * Why a lag and no cycle search: comparing with one kept generation costs one pass
+ * over the field per check and one slot, and finds every period that divides lag (16
+ * covers still lifes, blinkers and the period 2, 4, 8 and 16 oscillators; 30 the
+ * common 2, 3, 5, 6, 15); a search for an unknown period would have to keep, or
+ * recompute, every generation back to the cycle's start. */
+#define GOL_UNTIL_FINISH 1u
+typedef struct gol_until {
+    uint32_t struct_size;   /* in: sizeof(gol_until) of the caller, as gol_timing does */
+    uint32_t period;        /* out: minimal period found, 0 = none within max_generations */
+    uint64_t advanced;      /* out: g, the generation (counted from the call) whose field the
+                               engine holds, before any GOL_UNTIL_FINISH residue */
+    uint32_t lag, check_every; /* out: as used (check_every resolved from 0) */
+    uint32_t checks;        /* out: lag comparisons made */
+    uint32_t extra_generations; /* out: generations run beyond g to find the minimal period */
+} gol_until;
+gol_status gol_step_until_periodic(gol_engine* e, uint64_t max_generations, uint32_t lag,
+                                   uint32_t check_every, uint32_t flags, gol_until* out);
+
 /* ---- Multi-GPU, one process per GPU (replaces the MPI stripes :70-81 and the
  * halo exchange :104-145 with RCCL send/recv over xGMI) ---- */
 

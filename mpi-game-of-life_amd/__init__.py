@@ -42,7 +42,12 @@ EXPORTS = [
     "gol_activity_copied", "gol_activity_probed", "gol_activity_elided", "gol_torus_geometry", "gol_torus_pad",
     "gol_activity_pass_probed", "gol_plan_probe_tiles", "gol_activity_pass_kept",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
+    "gol_snapshot", "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
+    "gol_snapshot_drop", "gol_step_until_periodic",
 ]
+
+# gol_step_until_periodic flag: run on to max_generations once a period is known
+UNTIL_FINISH = 1
 
 # gol_plan_tuning's variants (plan.cpp kTuneVariantNames): 0 = the models' plan
 TUNE_VARIANTS = ["models", "no_half_strip", "skew_0.95", "skew_1.05", "other_block_kind"]
@@ -104,6 +109,22 @@ class PlanSummary(ctypes.Structure):
         ("handoff", ctypes.c_int32), ("tail_off", ctypes.c_int32),
         ("candidates", ctypes.c_uint32), ("passes", ctypes.c_uint32),
     ]
+
+
+class Until(ctypes.Structure):
+    """gol_until: what gol_step_until_periodic found."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),  # in: sizeof(gol_until) (gol.h)
+        ("period", ctypes.c_uint32),
+        ("advanced", ctypes.c_uint64),
+        ("lag", ctypes.c_uint32),
+        ("check_every", ctypes.c_uint32),
+        ("checks", ctypes.c_uint32),
+        ("extra_generations", ctypes.c_uint32),
+    ]
+
+    def __repr__(self):
+        return "Until(" + ", ".join(f"{k}={getattr(self, k)}" for k, _ in self._fields_[1:]) + ")"
 
 
 class SchedOp(ctypes.Structure):
@@ -217,7 +238,15 @@ def lib():
     L.gol_write_rect.argtypes = [vp, u64, u64, u64, u64, vp, u64, u32]
     L.gol_density.argtypes = [vp, u64, u64, u64, u64, u64, u64, vp, u64]
     L.gol_rect_blit.argtypes = [vp, u64, u64, vp, u64, u64, u64, u64, u32]
-    for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit"]:
+    L.gol_snapshot.argtypes = [vp]
+    L.gol_snapshot_same.argtypes = [vp, ctypes.POINTER(u32)]
+    L.gol_snapshot_diff.argtypes = [vp, pu64]
+    L.gol_snapshot_restore.argtypes = [vp]
+    L.gol_snapshot_drop.argtypes = [vp]
+    L.gol_step_until_periodic.argtypes = [vp, u64, u32, u32, u32, ctypes.POINTER(Until)]
+    for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit", "gol_snapshot",
+                 "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
+                 "gol_snapshot_drop", "gol_step_until_periodic"]:
         getattr(L, name).restype = ctypes.c_int
     for name in ["gol_torus_geometry", "gol_torus_pad", "gol_create", "gol_create_rank", "gol_load_ascii", "gol_store_ascii",
                  "gol_load_packed", "gol_store_packed", "gol_init_random", "gol_step",
@@ -544,6 +573,45 @@ class Engine:
 
     def sync(self):
         _check(lib().gol_sync(self._h))
+
+    def snapshot(self):
+        """Keeps a device copy of the field as it is now in the engine's one snapshot
+        slot (gol_snapshot; enqueued, replaces an earlier snapshot)."""
+        _check(lib().gol_snapshot(self._h))
+
+    def snapshot_same(self) -> bool:
+        """Whether every cell of the field equals the snapshot's (gol_snapshot_same;
+        waits for the engine's work, stops reading at the first difference)."""
+        v = ctypes.c_uint32()
+        _check(lib().gol_snapshot_same(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
+    def snapshot_diff(self) -> int:
+        """The exact number of cells that differ from the snapshot's (gol_snapshot_diff)."""
+        v = ctypes.c_uint64()
+        _check(lib().gol_snapshot_diff(self._h, ctypes.byref(v)))
+        return v.value
+
+    def snapshot_restore(self):
+        """Makes the field the snapshot's field again; the snapshot stays
+        (gol_snapshot_restore)."""
+        _check(lib().gol_snapshot_restore(self._h))
+
+    def snapshot_drop(self):
+        """Frees the snapshot slot (gol_snapshot_drop)."""
+        _check(lib().gol_snapshot_drop(self._h))
+
+    def step_until_periodic(self, max_generations, lag, check_every=0, finish=False):
+        """Steps until the field repeats with a period that divides `lag`, checking every
+        `check_every` generations (0: the least multiple of 64 >= lag), or for
+        max_generations (gol_step_until_periodic; uses the snapshot slot).  Returns an
+        Until: period (0 = none found), advanced (the generation the engine holds, before
+        the rest that finish=True runs to reach max_generations' field), lag,
+        check_every, checks, extra_generations."""
+        r = Until(struct_size=ctypes.sizeof(Until))
+        _check(lib().gol_step_until_periodic(self._h, max_generations, lag, check_every,
+                                             UNTIL_FINISH if finish else 0, ctypes.byref(r)))
+        return r
 
     def digest(self):
         live, hsh = ctypes.c_uint64(), ctypes.c_uint64()

@@ -1237,6 +1237,7 @@ void gol_destroy(gol_engine* e)
     if (e->d_acc) (void)hipFree(e->d_acc);
     if (e->d_flag) (void)hipFree(e->d_flag);
     if (e->rect_stage) (void)hipFree(e->rect_stage);
+    snapshot_free(e);
     for (const auto* pend : {&e->ev_pending, &e->ev_xpending})
         for (auto& p : *pend) {
             (void)hipEventDestroy(p.first);

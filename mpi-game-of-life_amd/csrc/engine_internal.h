@@ -10,6 +10,8 @@
 //                group engines
 //   torus.cpp    torus engines: ghost-zone geometry, wrap rounds around an inner
 //                dead-border engine, I/O and digests of the interior
+//   snapshot.cpp the snapshot slot: keep / compare / restore a generation on the
+//                device, and gol_step_until_periodic on top of the public calls
 // Mirrors main()'s flow in Parallel_Life_MPI.cpp:190-240: create
 // (readGridFromFile's allocation :88-89) -> load (:91-99) -> step (the epoch loop
 // :215-221 with the halo exchange :104-145) -> store (:157-164).
@@ -426,6 +428,13 @@ struct gol_engine {
 
     unsigned long long* d_acc = nullptr;
     int* d_flag = nullptr;  // ASCII codec error flag
+    // snapshot slot (snapshot.cpp, DESIGN §4 "Snapshots"): a copy of one whole field
+    // buffer, guard, halo and ghost rows included, allocated by the first gol_snapshot;
+    // snap_set: it holds a field.  A composite engine's stripes and a torus engine's
+    // inner engine hold the slots; the engine the caller sees holds none
+    uint64_t* snap = nullptr;
+    unsigned long long* snap_host = nullptr;  // pinned: where a comparison's answer lands
+    bool snap_set = false;
     // region I/O: device staging kept between calls (engine.cpp rect_stage)
     char* rect_stage = nullptr;
     size_t rect_stage_bytes = 0;
@@ -541,6 +550,9 @@ gol_status torus_write_rect(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, 
 gol_status torus_density(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uint64_t rw,
                          uint64_t by, uint64_t bx, uint64_t nby, uint64_t nbx, uint32_t* counts,
                          uint64_t cs);
+
+// ---- snapshot.cpp
+void snapshot_free(gol_engine* e);
 
 // ---- stripes.cpp
 uint32_t pick_depth(uint32_t K, uint64_t remaining);

@@ -25,6 +25,11 @@
 // applied in order after data.txt is loaded and before the first generation.
 // --window Y,X,H,W writes only that window to output.txt (gol_read_rect): H lines of
 // W cells; the file is truncated to them.  With --torus either may cross the seams.
+// --until-periodic LAG[:EVERY] runs the epochs with gol_step_until_periodic(epochs, LAG,
+// EVERY, GOL_UNTIL_FINISH): once generation g's field equals generation g - LAG's the
+// remaining generations are reduced modulo the period, so output.txt holds the bytes
+// the run without the flag writes; one extra line reports g and the period, or that
+// none was found.  One engine only: not with --ref-ranks, --gpus or --stripes.
 //
 // Deviation: where the reference prints an error and continues with
 // uninitialised values (:206) or an unopened file (:186), this program exits
@@ -84,10 +89,15 @@ void usage()
                  "           [--tb-depth K] [--rows-per-wave N] [--device D]\n"
                  "           [--gpus G] [--stripes S] [--halo-depth H] [--torus]\n"
                  "           [--paste FILE@Y,X[:set|or|xor|clear]]... [--window Y,X,H,W]\n"
+                 "           [--until-periodic LAG[:EVERY]]\n"
                  "Reads grid_size_data.txt and data.txt, writes output.txt.\n"
                  "--paste: combine the cells of FILE (lines of 0/1) into the loaded field at\n"
                  "         row Y, column X before stepping (default set); repeatable.\n"
                  "--window: output.txt holds only the H x W window at row Y, column X.\n"
+                 "--until-periodic: stop computing once the field repeats with a period that\n"
+                 "         divides LAG (checked every EVERY generations, default the next\n"
+                 "         multiple of 64); output.txt is the same.  Not with --ref-ranks,\n"
+                 "         --gpus or --stripes.\n"
                  "--torus: the field's opposite edges are joined (periodic boundary);\n"
                  "         not with --ref-ranks, nor with --gpus / --stripes above 1.\n";
 }
@@ -188,7 +198,8 @@ int main(int argc, char** argv)
     const auto t0 = std::chrono::steady_clock::now();  // MPI_Wtime() at :199
     std::string dir = ".";
     int gpus = 0, stripes = 0;
-    bool torus = false, ref_ranks = false, window = false;
+    bool torus = false, ref_ranks = false, window = false, until = false;
+    uint64_t lag_every[2] = {0, 0};  // --until-periodic LAG[:EVERY]
     uint64_t win[4] = {0, 0, 0, 0};  // Y, X, H, W
     std::vector<Paste> pastes;
     gol_config cfg;
@@ -232,6 +243,18 @@ int main(int argc, char** argv)
                 return 2;
             }
             window = true;
+        } else if (a == "--until-periodic") {
+            std::string v = next();
+            const size_t colon = v.find(':');
+            const bool ok = colon == std::string::npos
+                                ? parse_u64s(v, lag_every, 1)
+                                : parse_u64s(v.substr(0, colon), lag_every, 1) &&
+                                      parse_u64s(v.substr(colon + 1), lag_every + 1, 1);
+            if (!ok || lag_every[0] > UINT32_MAX || lag_every[1] > UINT32_MAX) {
+                std::cerr << "bad --until-periodic, want LAG[:EVERY]\n";
+                return 2;
+            }
+            until = true;
         } else if (a == "-h" || a == "--help") {
             usage();
             return 0;
@@ -249,6 +272,13 @@ int main(int argc, char** argv)
         }
         cfg.semantics = GOL_SEM_TORUS;
         gpus = stripes = 0;  // (--gpus 1 / --stripes 1: the one engine below)
+    }
+
+    if (until && (ref_ranks || gpus > 0 || stripes > 0)) {
+        std::cerr << "--until-periodic needs the one engine of one field; drop --ref-ranks, --gpus "
+                     "and --stripes"
+                  << std::endl;
+        return 2;
     }
 
     long long h = 0, w = 0, epochs = 0;
@@ -324,7 +354,9 @@ int main(int argc, char** argv)
             return 1;
         }
     }
-    if (epochs == 0 && !edits) {
+    gol_until found{};
+    found.struct_size = sizeof(gol_until);
+    if (epochs == 0 && !edits && !until) {
         // zero generations: the reference writes the input bytes back (:157-164)
         out = data;
     } else if (stripes > 0) {
@@ -356,7 +388,11 @@ int main(int argc, char** argv)
         gol_status st = gol_create((uint64_t)h, (uint64_t)w, &cfg, &e);
         if (st == GOL_OK) st = gol_load_ascii(e, data.data(), data.size());
         if (st == GOL_OK) st = paste_all({e});
-        if (st == GOL_OK && epochs > 0) st = gol_step(e, (uint64_t)epochs);
+        if (st == GOL_OK && until)
+            st = gol_step_until_periodic(e, (uint64_t)epochs, (uint32_t)lag_every[0],
+                                         (uint32_t)lag_every[1], GOL_UNTIL_FINISH, &found);
+        else if (st == GOL_OK && epochs > 0)
+            st = gol_step(e, (uint64_t)epochs);
         if (st == GOL_OK) st = gol_sync(e);
         if (st == GOL_OK) st = window ? read_window({e}, out) : gol_store_ascii(e, out.data(), out.size());
         if (st != GOL_OK) {
@@ -365,6 +401,16 @@ int main(int argc, char** argv)
             return 1;
         }
         gol_destroy(e);
+    }
+
+    if (until) {
+        if (found.period)
+            std::cout << "Period " << found.period << " from generation " << found.advanced
+                      << " on (lag " << found.lag << ", checked every " << found.check_every
+                      << " generations)." << std::endl;
+        else
+            std::cout << "No period dividing " << found.lag << " within " << epochs
+                      << " generations (checked every " << found.check_every << ")." << std::endl;
     }
 
     // writeDataToFile (:166-183): create if missing, never truncate, each rank's

@@ -319,6 +319,29 @@ struct ProbeArgs {
 };
 hipError_t launch_probe_pass(const ProbeArgs& a, RuleKind rule, hipStream_t s);
 
+// The snapshot compare (life_snap.hip, DESIGN §4 "Snapshots"): `rows` buffer rows from
+// row_base on, `nwords` stored words per row from word0 on, of the engine's current
+// buffer against the same words of its snapshot, over the copy pass's tiles
+// (kCopyTileRows x kCopyTileWords, column segments fastest).  A leaf's own rows: word0
+// = 0 and the field's words; a torus interior: row tG, word tGx of the inner engine.
+// mask: the stored-form valid bits of words nwords - 2 and nwords - 1 (the last lane
+// group: all ones and lastmask_split[0] with 2 planes, both lastmask_split words with
+// 4).  count = false: *flag (zeroed by the caller on the stream) is set to 1 when any
+// word differs (one store per workgroup at most), and wavefronts that find it set
+// leave out their field loads; count
+// = true: the differing cells are added to *count, one atomic per workgroup at most.
+struct SnapArgs {
+    const uint64_t* cur;   // row 0 of the current buffer and of the snapshot
+    const uint64_t* snap;
+    int64_t stride;        // words per buffer row
+    int64_t row_base, word0, nwords, rows;
+    uint64_t mask[2];
+    uint32_t* flag;
+    unsigned long long* count;
+    int32_t ntile, ncol;   // set by launch_snap_compare
+};
+hipError_t launch_snap_compare(const SnapArgs& a, bool count, hipStream_t s);
+
 // Resident 256-thread blocks per CU of the stencil kernel (occupancy query).
 // mp: of the multi-pass kernels (0 where none exists)
 int life_blocks_per_cu(int depth, RuleKind rule, int planes, bool hand, bool mp = false);
