@@ -204,3 +204,34 @@ def test_errors(pkg):
         for name in calls:
             estate(getattr(g.members[1], name))
         estate(lambda: g.members[0].step_until_periodic(10, 1))
+
+
+@pytest.mark.parametrize("shape", [(1, 127), (8, 128), (9, 129), (37, 500)])
+def test_four_planes(pkg, oracle, shape):
+    """The compare of an NP = 4 leaf (leaf_view: both words of the last lane group
+    masked): only a library built with the 4-plane kernels (the dev build, through
+    GOL_LIB) creates such an engine."""
+    h, w = shape
+    try:
+        e = pkg.Engine(h, w, rule=CONWAY, device=0, word_planes=4, streams=1)
+    except pkg.GolError as err:
+        assert err.status == pkg.GOL_EINVAL
+        pytest.skip("the loaded library has no 4-plane kernels")
+    with e:
+        assert e.word_planes == 4
+        a, b = oracle.bp_random(h, w, 17), oracle.bp_random(h, w, 18)
+        e.load_packed(a)
+        e.snapshot()
+        assert e.snapshot_same() is True and e.snapshot_diff() == 0
+        # either word of a lane group, the group's edges, the last column
+        for x in sorted({x for x in (0, 63, 64, 127, 128, w - 1) if x < w}):
+            for y in sorted({0, h - 1}):
+                e.write_rect(y, x, ONE, 1, pkg.RECT_XOR)
+                assert e.snapshot_diff() == 1, (y, x)
+                assert e.snapshot_same() is False, (y, x)
+                e.write_rect(y, x, ONE, 1, pkg.RECT_XOR)
+                assert e.snapshot_diff() == 0 and e.snapshot_same() is True, (y, x)
+        e.load_packed(b)
+        assert e.snapshot_diff() == popcount(a ^ b)
+        e.snapshot_restore()
+        assert (e.store_packed() == a).all()
