@@ -88,6 +88,20 @@ def test_autotune_respects_waiting_kernel_registry(pkg, oracle, autotune):
         b.close()
 
 
+def test_autotune_keeps_the_skip_without_births(pkg, autotune):
+    """B/S2 (no births: every field freezes) at 65536^2, the benchmark's engine: the
+    autotuner times computing launches only, so the hand-off variant, which cannot
+    skip, is no candidate where the models' plan can; the frozen field's launches
+    then skip.  (Before r16 one create in eleven picked it on a 3% margin and a
+    step of 1000 generations took 28 ms instead of 0.29.)"""
+    with pkg.Engine(W, W, device=0) as e:
+        assert e.tuning[0] != "other_block_kind" and not e.handoff, e.tuning
+        e.init_random(1)
+        e.step(6 * 16)
+        computed, skipped = e.activity()
+        assert skipped > 0 and computed > 0
+
+
 # ---- every variant the autotuner can pick, forced (GOL_DEV_PLAN_VARIANT) ----
 # build_plans makes the named variant of every full-depth plan and runs it in
 # place of the models' plan, untimed.  A variant that equals the models' plan at
