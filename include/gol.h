@@ -474,6 +474,79 @@ typedef struct gol_until {
 gol_status gol_step_until_periodic(gol_engine* e, uint64_t max_generations, uint32_t lag,
                                    uint32_t check_every, uint32_t flags, gol_until* out);
 
+/* ---- Batches: many small independent fields stepped in one launch ----
+ * A gol_batch holds n fields of the same h x w, the same rule and the same boundary on
+ * one device and advances all of them with one kernel launch per step: a lane holds a
+ * 64-column word of a field and all its rows in registers, so a 64 x 64 field is one
+ * lane, a wavefront 64 fields, and between a launch's loads and stores nothing touches
+ * memory.  Every field evolves exactly as an h x w gol_create engine would.
+ * Create: cfg supplies birth_mask, survive_mask, device and semantics.  GOL_SEM_GLOBAL
+ * gives every field a dead border; GOL_SEM_TORUS joins every field's opposite edges, for
+ * any h, w >= 1, by the torus engine's definition (a field so small that a cell is its
+ * own neighbour included); GOL_SEM_REF_STRIPES is GOL_EINVAL.  Every other gol_config
+ * field must be 0 (ref_ranks: 0 or gol_config_init's 1), else GOL_EINVAL: a batch has no
+ * plan knobs.
+ * Limits: 1 <= h <= 64, 1 <= w <= 4096, n >= 1 and n * lanes_per_field <= 2^31; beyond
+ * them GOL_EINVAL with a message that names gol_create, the engine for larger fields.
+ * Like gol_create, bad arguments are rejected before the GPU is touched.
+ * Geometry (fixed): lanes_per_field = the least power of two >= ceil(w/64),
+ * fields_per_wave = 64 / lanes_per_field, rows_in_regs = the least of {8, 16, 32, 64}
+ * that is >= h, waves = ceil(n / fields_per_wave).
+ * I/O: fields [first, first + count), canonical packed words as gol_load_packed's: word
+ * q of row r of field first + i at words[i * field_stride_words + r * row_stride_words
+ * + q]; row_stride_words >= ceil(w/64), field_stride_words >= h * row_stride_words and
+ * first + count <= n, else GOL_EINVAL; count == 0 is GOL_OK with nothing done.  Bits of
+ * the input at columns >= w are ignored, and a store writes 0 there.  Every I/O call and
+ * gol_batch_digest returns after the caller's buffer has been consumed or filled, as
+ * gol_read_rect does.  The _device forms take a device pointer on the batch's device and
+ * move nothing to the host; the caller makes sure its own work on that buffer has
+ * finished before the call.  The host forms are the device forms behind a staging
+ * buffer.
+ * Errors go through gol_status and gol_last_error; a handle is not thread-safe; the
+ * batch owns its stream and its memory. */
+typedef struct gol_batch gol_batch;
+
+/* Host-only, no GPU: the geometry gol_batch_create would use (the same GOL_EINVALs).
+ * Out pointers may be NULL. */
+gol_status gol_batch_geometry(uint64_t n, uint64_t h, uint64_t w, const gol_config* cfg,
+                              uint32_t* lanes_per_field, uint32_t* fields_per_wave,
+                              uint32_t* rows_in_regs, uint64_t* waves);
+/* All fields start dead.  GOL_DEV_BATCH_LAUNCH_GENS=<k> in the environment sets the
+ * launch cap (gol_batch_step) of the batch being created. */
+gol_status gol_batch_create(uint64_t n, uint64_t h, uint64_t w, const gol_config* cfg,
+                            gol_batch** out);
+void gol_batch_destroy(gol_batch* b);
+/* The batch as created; *launch_generations is the launch cap.  Out pointers may be NULL. */
+gol_status gol_batch_info(gol_batch* b, uint64_t* n, uint64_t* h, uint64_t* w,
+                          uint32_t* lanes_per_field, uint32_t* fields_per_wave,
+                          uint32_t* rows_in_regs, uint32_t* launch_generations);
+
+gol_status gol_batch_load_packed(gol_batch* b, uint64_t first, uint64_t count,
+                                 const uint64_t* words, uint64_t field_stride_words,
+                                 uint64_t row_stride_words);
+gol_status gol_batch_store_packed(gol_batch* b, uint64_t first, uint64_t count, uint64_t* words,
+                                  uint64_t field_stride_words, uint64_t row_stride_words);
+gol_status gol_batch_load_device(gol_batch* b, uint64_t first, uint64_t count,
+                                 const uint64_t* words, uint64_t field_stride_words,
+                                 uint64_t row_stride_words);
+gol_status gol_batch_store_device(gol_batch* b, uint64_t first, uint64_t count, uint64_t* words,
+                                  uint64_t field_stride_words, uint64_t row_stride_words);
+
+/* Field i becomes exactly what gol_init_random(e, seed + i) gives an h x w engine.
+ * Enqueued like a step. */
+gol_status gol_batch_init_random(gol_batch* b, uint64_t seed);
+
+/* Advances every field `generations` generations in ceil(generations /
+ * launch_generations) launches (default cap 4096, so that no single launch holds a
+ * shared GPU for long).  Returns after the work is enqueued; gol_batch_sync waits. */
+gol_status gol_batch_step(gol_batch* b, uint64_t generations);
+gol_status gol_batch_sync(gol_batch* b);
+
+/* live[i], hash[i] = exactly what gol_digest returns for an h x w engine that holds
+ * field first + i (either array may be NULL).  Only 2 * count words cross to the host. */
+gol_status gol_batch_digest(gol_batch* b, uint64_t first, uint64_t count, uint64_t* live,
+                            uint64_t* hash);
+
 /* ---- Multi-GPU, one process per GPU (replaces the MPI stripes :70-81 and the
  * halo exchange :104-145 with RCCL send/recv over xGMI) ---- */
 

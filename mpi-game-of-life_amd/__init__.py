@@ -44,6 +44,10 @@ EXPORTS = [
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
     "gol_snapshot", "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
     "gol_snapshot_drop", "gol_step_until_periodic",
+    "gol_batch_geometry", "gol_batch_create", "gol_batch_destroy", "gol_batch_info",
+    "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
+    "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step", "gol_batch_sync",
+    "gol_batch_digest",
 ]
 
 # gol_step_until_periodic flag: run on to max_generations once a period is known
@@ -244,6 +248,24 @@ def lib():
     L.gol_snapshot_restore.argtypes = [vp]
     L.gol_snapshot_drop.argtypes = [vp]
     L.gol_step_until_periodic.argtypes = [vp, u64, u32, u32, u32, ctypes.POINTER(Until)]
+    pu32 = ctypes.POINTER(u32)
+    L.gol_batch_geometry.argtypes = [u64, u64, u64, ctypes.POINTER(Config), pu32, pu32, pu32, pu64]
+    L.gol_batch_create.argtypes = [u64, u64, u64, ctypes.POINTER(Config), ctypes.POINTER(vp)]
+    L.gol_batch_destroy.argtypes = [vp]
+    L.gol_batch_destroy.restype = None
+    L.gol_batch_info.argtypes = [vp, pu64, pu64, pu64, pu32, pu32, pu32, pu32]
+    for name in ["gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
+                 "gol_batch_store_device"]:
+        getattr(L, name).argtypes = [vp, u64, u64, vp, u64, u64]
+    L.gol_batch_init_random.argtypes = [vp, u64]
+    L.gol_batch_step.argtypes = [vp, u64]
+    L.gol_batch_sync.argtypes = [vp]
+    L.gol_batch_digest.argtypes = [vp, u64, u64, vp, vp]
+    for name in ["gol_batch_geometry", "gol_batch_create", "gol_batch_info",
+                 "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
+                 "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step",
+                 "gol_batch_sync", "gol_batch_digest"]:
+        getattr(L, name).restype = ctypes.c_int
     for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit", "gol_snapshot",
                  "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
                  "gol_snapshot_drop", "gol_step_until_periodic"]:
@@ -410,6 +432,18 @@ def rect_blit(src, sx, dst, dx, rows, cols, op=RECT_SET):
     _check(lib().gol_rect_blit(a.ctypes.data, a.shape[1], sx, dst.ctypes.data, dst.shape[1], dx,
                                rows, cols, op))
     return dst
+
+
+def batch_geometry(n, h, w, **cfg_kw):
+    """gol_batch_geometry (host only, no GPU): the geometry BatchEngine(n, h, w, ...)
+    would use.  Returns a dict: lanes_per_field, fields_per_wave, rows_in_regs, waves."""
+    cfg = make_config(**cfg_kw)
+    lpf, fpw, rows = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    waves = ctypes.c_uint64()
+    _check(lib().gol_batch_geometry(n, h, w, ctypes.byref(cfg), ctypes.byref(lpf),
+                                    ctypes.byref(fpw), ctypes.byref(rows), ctypes.byref(waves)))
+    return {"lanes_per_field": lpf.value, "fields_per_wave": fpw.value,
+            "rows_in_regs": rows.value, "waves": waves.value}
 
 
 def unique_id() -> bytes:
@@ -690,6 +724,124 @@ class Engine:
             raise GolError(GOL_ESTATE, f"libgol.so's gol_timing is {t.struct_size} bytes, "
                                        f"this binding's {ctypes.sizeof(Timing)}")
         return {k: getattr(t, k) for k, _ in Timing._fields_ if k != "struct_size"}
+
+
+class BatchEngine:
+    """n independent h x w fields of one rule and one boundary (SEM_GLOBAL: a dead
+    border per field, SEM_TORUS: a torus per field) on one GPU, advanced together by
+    one launch per step (gol_batch).  Fields are packed uint64 arrays of shape
+    [count, h, ceil(w/64)], or contiguous torch.int64 CUDA tensors of that shape."""
+
+    def __init__(self, n, h, w, rule=REF_RULE, device=-1, semantics=SEM_GLOBAL):
+        self.n, self.h, self.w, self.device = n, h, w, device
+        self.wq = (w + 63) // 64
+        self._h = None
+        cfg = make_config(rule, device, semantics)
+        handle = ctypes.c_void_p()
+        _check(lib().gol_batch_create(n, h, w, ctypes.byref(cfg), ctypes.byref(handle)))
+        self._h = handle
+        lpf, fpw, rows, lg = (ctypes.c_uint32() for _ in range(4))
+        _check(lib().gol_batch_info(self._h, None, None, None, ctypes.byref(lpf),
+                                    ctypes.byref(fpw), ctypes.byref(rows), ctypes.byref(lg)))
+        self._info = {"n": n, "h": h, "w": w, "lanes_per_field": lpf.value,
+                      "fields_per_wave": fpw.value, "rows_in_regs": rows.value,
+                      "launch_generations": lg.value}
+
+    @property
+    def info(self):
+        """n, h, w, lanes_per_field, fields_per_wave, rows_in_regs and
+        launch_generations (the launch cap) of the batch as created."""
+        return dict(self._info)
+
+    lanes_per_field = property(lambda self: self._info["lanes_per_field"])
+    fields_per_wave = property(lambda self: self._info["fields_per_wave"])
+    rows_in_regs = property(lambda self: self._info["rows_in_regs"])
+    launch_generations = property(lambda self: self._info["launch_generations"])
+
+    def close(self):
+        if self._h:
+            lib().gol_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _count(self, first, count):
+        return self.n - first if count is None else count
+
+    def load_packed(self, arr, first=0):
+        """Fields [first, first + len(arr)) from a uint64 array [count, h, >= ceil(w/64)]
+        (bits at columns >= w are ignored)."""
+        import numpy as np
+        a = np.ascontiguousarray(arr, dtype=np.uint64)
+        if a.ndim != 3 or a.shape[1] != self.h:
+            raise GolError(GOL_EINVAL, "fields must be a uint64 array [count, h, words]")
+        _check(lib().gol_batch_load_packed(self._h, first, a.shape[0], a.ctypes.data,
+                                           a.shape[1] * a.shape[2], a.shape[2]))
+
+    def store_packed(self, first=0, count=None):
+        """Fields [first, first + count) as a uint64 array [count, h, ceil(w/64)]."""
+        import numpy as np
+        count = self._count(first, count)
+        a = np.zeros((max(count, 0), self.h, self.wq), dtype=np.uint64)
+        _check(lib().gol_batch_store_packed(self._h, first, count, a.ctypes.data,
+                                            self.h * self.wq, self.wq))
+        return a
+
+    def load_tensor(self, t, first=0):
+        """load_packed from a contiguous torch.int64 CUDA tensor [count, h, ceil(w/64)]
+        on the batch's device (gol_batch_load_device: nothing crosses to the host).
+        Waits for torch's current stream first."""
+        import torch
+        if (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.dim() != 3
+                or t.shape[1] != self.h or t.shape[2] != self.wq):
+            raise GolError(GOL_EINVAL, "fields must be a contiguous torch.int64 CUDA tensor "
+                                       "[count, h, ceil(w/64)]")
+        torch.cuda.current_stream(t.device).synchronize()
+        _check(lib().gol_batch_load_device(self._h, first, t.shape[0], t.data_ptr(),
+                                           self.h * self.wq, self.wq))
+
+    def store_tensor(self, first=0, count=None):
+        """store_packed into a new contiguous torch.int64 CUDA tensor [count, h,
+        ceil(w/64)] on the batch's device (gol_batch_store_device; with device=-1 at
+        create that is taken to be torch's current device)."""
+        import torch
+        count = self._count(first, count)
+        dev = torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
+        t = torch.zeros((max(count, 0), self.h, self.wq), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(t.device).synchronize()
+        _check(lib().gol_batch_store_device(self._h, first, count, t.data_ptr(),
+                                            self.h * self.wq, self.wq))
+        return t
+
+    def init_random(self, seed=1):
+        """Field i = Engine(h, w).init_random(seed + i)'s field."""
+        _check(lib().gol_batch_init_random(self._h, seed))
+
+    def step(self, gens):
+        _check(lib().gol_batch_step(self._h, gens))
+
+    def sync(self):
+        _check(lib().gol_batch_sync(self._h))
+
+    def digest(self, first=0, count=None):
+        """(live, hash): two uint64 arrays [count], per field what Engine.digest()
+        returns for an h x w engine holding it."""
+        import numpy as np
+        count = self._count(first, count)
+        live = np.zeros(max(count, 0), dtype=np.uint64)
+        hsh = np.zeros(max(count, 0), dtype=np.uint64)
+        _check(lib().gol_batch_digest(self._h, first, count, live.ctypes.data, hsh.ctypes.data))
+        return live, hsh
 
 
 def _make_transport(fn):

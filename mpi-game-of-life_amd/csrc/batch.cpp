@@ -1,0 +1,358 @@
+// batch.cpp -- gol_batch: n independent h x w fields of one rule and one boundary,
+// held on the device in the batch kernel's order and advanced together by one
+// life_batch_kernel launch per (at most) launch_generations generations (life_batch.h,
+// DESIGN §4 "life_batch_kernel").  Argument checks and the fixed geometry are host
+// code that never touches the GPU; the host forms of load and store are the device
+// forms behind a compact staging buffer.
+#include <cstdlib>
+
+#include "engine_internal.h"
+#include "life_batch.h"
+
+struct gol_batch {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint64_t n = 0, h = 0, w = 0, wq = 0, waves = 0;
+    uint32_t lpf = 1, lpf_shift = 0, fpw = 64, rows = 8;
+    uint32_t launch_gens = 0;
+    uint32_t birth = 0, survive = 0, sem = GOL_SEM_GLOBAL;
+    gol::RuleKind rule = gol::RULE_REF;
+    uint64_t* buf = nullptr;
+    // staging for the host forms of load / store and for the digests, kept between calls
+    uint64_t* stage = nullptr;
+    size_t stage_words = 0;
+};
+
+namespace golh __attribute__((visibility("hidden"))) {
+
+namespace {
+
+// Generations per launch unless GOL_DEV_BATCH_LAUNCH_GENS says otherwise: a launch of
+// the 64-row B3/S23 kernel stays far below 100 ms.
+constexpr uint32_t kBatchLaunchGens = 4096;
+
+struct BatchShape {
+    uint32_t lpf, lpf_shift, fpw, rows;
+    uint64_t wq, waves;
+};
+
+// The checks and the geometry gol_batch_geometry and gol_batch_create share.
+gol_status batch_shape(uint64_t n, uint64_t h, uint64_t w, const gol_config* cfg, BatchShape* s)
+{
+    if (!cfg) return fail(GOL_EINVAL, "null config");
+    if (cfg->birth_mask >= 512 || cfg->survive_mask >= 512)
+        return fail(GOL_EINVAL, "rule masks are 9-bit");
+    if (cfg->semantics != GOL_SEM_GLOBAL && cfg->semantics != GOL_SEM_TORUS)
+        return fail(GOL_EINVAL, "a batch is GOL_SEM_GLOBAL (dead border per field) or "
+                                "GOL_SEM_TORUS (torus per field)");
+    if (cfg->ref_ranks > 1 || cfg->tb_depth || cfg->halo_depth || cfg->rows_per_wave ||
+        cfg->handoff || cfg->streams || cfg->strip_lanes || cfg->word_planes || cfg->resident ||
+        cfg->exchange_overlap)
+        return fail(GOL_EINVAL, "a batch has no plan knobs: every gol_config field but the rule, "
+                                "device and semantics must be 0");
+    if (n == 0 || h == 0 || w == 0) return fail(GOL_EINVAL, "n, h and w must be >= 1");
+    if (h > 64 || w > 4096)
+        return fail(GOL_EINVAL, "a batch holds fields of at most 64 rows x 4096 columns; "
+                                "gol_create is the engine for larger fields");
+    s->wq = (w + 63) / 64;
+    s->lpf = 1;
+    s->lpf_shift = 0;
+    while (s->lpf < s->wq) {
+        s->lpf *= 2;
+        s->lpf_shift += 1;
+    }
+    s->fpw = 64 / s->lpf;
+    s->rows = 8;
+    while (s->rows < h) s->rows *= 2;
+    if (n > (1ull << 31) / s->lpf)
+        return fail(GOL_EINVAL, "batch too large: n * lanes_per_field must be <= 2^31; "
+                                "gol_create is the engine for larger fields");
+    s->waves = (n + s->fpw - 1) / s->fpw;
+    return GOL_OK;
+}
+
+gol::BatchGeom geom_of(const gol_batch* b)
+{
+    return gol::BatchGeom{b->buf, (int64_t)b->n, (int32_t)b->h, (int32_t)b->wq,
+                          (int32_t)b->lpf_shift, last_mask(b->w)};
+}
+
+gol_status check_range(const gol_batch* b, uint64_t first, uint64_t count, const void* words,
+                       uint64_t fs, uint64_t rs)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (first > b->n || count > b->n - first)
+        return fail(GOL_EINVAL, "first + count exceeds the batch's fields");
+    if (rs < b->wq) return fail(GOL_EINVAL, "row_stride_words < ceil(w/64)");
+    if (fs < b->h * rs) return fail(GOL_EINVAL, "field_stride_words < h * row_stride_words");
+    if (count && !words) return fail(GOL_EINVAL, "null words");
+    return GOL_OK;
+}
+
+gol_status need_stage(gol_batch* b, size_t words)
+{
+    if (b->stage_words >= words) return GOL_OK;
+    if (b->stage) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        (void)hipFree(b->stage);
+        b->stage = nullptr;
+        b->stage_words = 0;
+    }
+    HIP_TRY(hipMalloc(&b->stage, words * sizeof(uint64_t)));
+    b->stage_words = words;
+    return GOL_OK;
+}
+
+// Host words <-> the compact staging image ([count][h][wq] words): one linear copy when
+// the caller's image has no padding, one 2-D copy when its fields follow each other row
+// after row, else one 2-D copy per field.
+gol_status stage_copy(gol_batch* b, uint64_t count, uint64_t* host, uint64_t fs, uint64_t rs,
+                      bool to_device)
+{
+    const size_t rowb = b->wq * 8;
+    if (rs == b->wq && fs == b->h * rs) {
+        // the caller's image is the staging image: one linear copy
+        const size_t bytes = (size_t)count * b->h * rowb;
+        if (to_device)
+            HIP_TRY(hipMemcpyAsync(b->stage, host, bytes, hipMemcpyHostToDevice, b->stream));
+        else
+            HIP_TRY(hipMemcpyAsync(host, b->stage, bytes, hipMemcpyDeviceToHost, b->stream));
+        return GOL_OK;
+    }
+    const bool flat = fs == b->h * rs;
+    const uint64_t pieces = flat ? 1 : count, rows = flat ? count * b->h : b->h;
+    for (uint64_t i = 0; i < pieces; ++i) {
+        uint64_t* hp = host + i * fs;
+        uint64_t* dp = b->stage + i * b->h * b->wq;
+        if (to_device)
+            HIP_TRY(hipMemcpy2DAsync(dp, rowb, hp, rs * 8, rowb, rows, hipMemcpyHostToDevice,
+                                     b->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(hp, rs * 8, dp, rowb, rowb, rows, hipMemcpyDeviceToHost,
+                                     b->stream));
+    }
+    return GOL_OK;
+}
+
+}  // namespace
+
+}  // namespace golh
+
+extern "C" {
+
+gol_status gol_batch_geometry(uint64_t n, uint64_t h, uint64_t w, const gol_config* cfg,
+                              uint32_t* lanes_per_field, uint32_t* fields_per_wave,
+                              uint32_t* rows_in_regs, uint64_t* waves)
+{
+    BatchShape s{};
+    GOL_TRY(batch_shape(n, h, w, cfg, &s));
+    if (lanes_per_field) *lanes_per_field = s.lpf;
+    if (fields_per_wave) *fields_per_wave = s.fpw;
+    if (rows_in_regs) *rows_in_regs = s.rows;
+    if (waves) *waves = s.waves;
+    return GOL_OK;
+}
+
+gol_status gol_batch_create(uint64_t n, uint64_t h, uint64_t w, const gol_config* cfg,
+                            gol_batch** out)
+{
+    if (!out) return fail(GOL_EINVAL, "null out");
+    *out = nullptr;
+    BatchShape s{};
+    GOL_TRY(batch_shape(n, h, w, cfg, &s));
+    uint32_t launch_gens = kBatchLaunchGens;
+    if (const char* v = std::getenv("GOL_DEV_BATCH_LAUNCH_GENS")) {
+        const long k = std::atol(v);
+        if (k < 1 || k > (1l << 30))
+            return fail(GOL_EINVAL, "GOL_DEV_BATCH_LAUNCH_GENS must be in 1..2^30");
+        launch_gens = (uint32_t)k;
+    }
+    gol_batch* b = new (std::nothrow) gol_batch();
+    if (!b) return fail(GOL_ENOMEM, "host allocation");
+    b->n = n;
+    b->h = h;
+    b->w = w;
+    b->wq = s.wq;
+    b->waves = s.waves;
+    b->lpf = s.lpf;
+    b->lpf_shift = s.lpf_shift;
+    b->fpw = s.fpw;
+    b->rows = s.rows;
+    b->launch_gens = launch_gens;
+    b->birth = cfg->birth_mask;
+    b->survive = cfg->survive_mask;
+    b->sem = cfg->semantics;
+    b->rule = (b->birth == GOL_REF_BIRTH && b->survive == GOL_REF_SURVIVE) ? gol::RULE_REF
+              : (b->birth == GOL_CONWAY_BIRTH && b->survive == GOL_CONWAY_SURVIVE)
+                  ? gol::RULE_CONWAY
+                  : gol::RULE_GENERIC;
+    auto init = [&]() -> gol_status {
+        if (cfg->device >= 0) HIP_TRY(hipSetDevice(cfg->device));
+        HIP_TRY(hipGetDevice(&b->device));
+        HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        const size_t bytes = (size_t)b->waves * b->h * 64 * sizeof(uint64_t);
+        HIP_TRY(hipMalloc(&b->buf, bytes));
+        // padding lanes and the lanes beyond field n - 1 stay 0 from here on
+        HIP_TRY(hipMemsetAsync(b->buf, 0, bytes, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        return GOL_OK;
+    };
+    const gol_status st = init();
+    if (st != GOL_OK) {
+        const std::string msg = g_last_error;
+        gol_batch_destroy(b);
+        g_last_error = msg;
+        return st;
+    }
+    *out = b;
+    return GOL_OK;
+}
+
+void gol_batch_destroy(gol_batch* b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->buf) (void)hipFree(b->buf);
+    if (b->stage) (void)hipFree(b->stage);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+gol_status gol_batch_info(gol_batch* b, uint64_t* n, uint64_t* h, uint64_t* w,
+                          uint32_t* lanes_per_field, uint32_t* fields_per_wave,
+                          uint32_t* rows_in_regs, uint32_t* launch_generations)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (n) *n = b->n;
+    if (h) *h = b->h;
+    if (w) *w = b->w;
+    if (lanes_per_field) *lanes_per_field = b->lpf;
+    if (fields_per_wave) *fields_per_wave = b->fpw;
+    if (rows_in_regs) *rows_in_regs = b->rows;
+    if (launch_generations) *launch_generations = b->launch_gens;
+    return GOL_OK;
+}
+
+gol_status gol_batch_load_device(gol_batch* b, uint64_t first, uint64_t count,
+                                 const uint64_t* words, uint64_t field_stride_words,
+                                 uint64_t row_stride_words)
+{
+    GOL_TRY(check_range(b, first, count, words, field_stride_words, row_stride_words));
+    if (count == 0) return GOL_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(gol::launch_batch_load(geom_of(b), (int64_t)first, (int64_t)count, words,
+                                   (int64_t)field_stride_words, (int64_t)row_stride_words,
+                                   b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+gol_status gol_batch_store_device(gol_batch* b, uint64_t first, uint64_t count, uint64_t* words,
+                                  uint64_t field_stride_words, uint64_t row_stride_words)
+{
+    GOL_TRY(check_range(b, first, count, words, field_stride_words, row_stride_words));
+    if (count == 0) return GOL_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(gol::launch_batch_store(geom_of(b), (int64_t)first, (int64_t)count, words,
+                                    (int64_t)field_stride_words, (int64_t)row_stride_words,
+                                    b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+gol_status gol_batch_load_packed(gol_batch* b, uint64_t first, uint64_t count,
+                                 const uint64_t* words, uint64_t field_stride_words,
+                                 uint64_t row_stride_words)
+{
+    GOL_TRY(check_range(b, first, count, words, field_stride_words, row_stride_words));
+    if (count == 0) return GOL_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    GOL_TRY(need_stage(b, (size_t)(count * b->h * b->wq)));
+    GOL_TRY(stage_copy(b, count, const_cast<uint64_t*>(words), field_stride_words,
+                       row_stride_words, true));
+    HIP_TRY(gol::launch_batch_load(geom_of(b), (int64_t)first, (int64_t)count, b->stage,
+                                   (int64_t)(b->h * b->wq), (int64_t)b->wq, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+gol_status gol_batch_store_packed(gol_batch* b, uint64_t first, uint64_t count, uint64_t* words,
+                                  uint64_t field_stride_words, uint64_t row_stride_words)
+{
+    GOL_TRY(check_range(b, first, count, words, field_stride_words, row_stride_words));
+    if (count == 0) return GOL_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    GOL_TRY(need_stage(b, (size_t)(count * b->h * b->wq)));
+    HIP_TRY(gol::launch_batch_store(geom_of(b), (int64_t)first, (int64_t)count, b->stage,
+                                    (int64_t)(b->h * b->wq), (int64_t)b->wq, b->stream));
+    GOL_TRY(stage_copy(b, count, words, field_stride_words, row_stride_words, false));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+gol_status gol_batch_init_random(gol_batch* b, uint64_t seed)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(gol::launch_batch_init_random(geom_of(b), seed, b->stream));
+    return GOL_OK;
+}
+
+gol_status gol_batch_step(gol_batch* b, uint64_t generations)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (generations == 0) return GOL_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    gol::BatchArgs a{};
+    a.buf = b->buf;
+    a.waves = (int64_t)b->waves;
+    a.n = (int64_t)b->n;
+    a.h = (int32_t)b->h;
+    a.w = (int32_t)b->w;
+    a.wq = (int32_t)b->wq;
+    a.lpf_shift = (int32_t)b->lpf_shift;
+    a.torus = b->sem == GOL_SEM_TORUS;
+    a.birth = b->birth;
+    a.survive = b->survive;
+    a.lastmask = gol_split64(last_mask(b->w));
+    for (uint64_t left = generations; left > 0;) {
+        const uint64_t g = std::min<uint64_t>(left, b->launch_gens);
+        a.gens = (int32_t)g;
+        HIP_TRY(gol::launch_batch(a, (int)b->rows, b->rule, b->stream));
+        left -= g;
+    }
+    return GOL_OK;
+}
+
+gol_status gol_batch_sync(gol_batch* b)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+gol_status gol_batch_digest(gol_batch* b, uint64_t first, uint64_t count, uint64_t* live,
+                            uint64_t* hash)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (first > b->n || count > b->n - first)
+        return fail(GOL_EINVAL, "first + count exceeds the batch's fields");
+    if (count == 0) return GOL_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    GOL_TRY(need_stage(b, (size_t)(2 * count)));
+    HIP_TRY(gol::launch_batch_digest(geom_of(b), (int64_t)first, (int64_t)count, b->stage,
+                                     b->stream));
+    std::vector<uint64_t> pairs(2 * count);
+    HIP_TRY(hipMemcpyAsync(pairs.data(), b->stage, 2 * count * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (uint64_t i = 0; i < count; ++i) {
+        if (live) live[i] = pairs[2 * i];
+        if (hash) hash[i] = pairs[2 * i + 1];
+    }
+    return GOL_OK;
+}
+
+}  // extern "C"
