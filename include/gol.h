@@ -277,6 +277,36 @@ gol_status gol_activity_pass_probed(gol_engine* e, uint64_t* pass_probed_units);
  * Torus engines wrap before every round: their count stays 0. */
 gol_status gol_activity_pass_kept(gol_engine* e, uint64_t* kept_tiles);
 
+/* Sure tiles (DESIGN.md section 4 "Sure tiles").  Where the step before ended with a
+ * remainder launch (fewer than tb_depth generations), a unit that launch found calm
+ * also keeps its state for one more generation, so a tile of the next step's probe
+ * pass all of whose owners were calm there is known to keep its state: it counts as
+ * kept and leaves before it loads a field word.  gol_activity_pass_sure returns how
+ * many of the tile passes gol_activity_pass_kept counts left that way since create or
+ * gol_reset_timing.  No field word and no other counter depends on it;
+ * GOL_DEV_TWIN_SURE=0 at create turns it off (every kept tile loads its rows and
+ * compares, as before; the count stays 0), and so does whatever turns
+ * gol_activity_pass_kept off. */
+gol_status gol_activity_pass_sure(gol_engine* e, uint64_t* sure_tiles);
+
+/* Short step (DESIGN.md section 4 "Short step").  When gol_sync finds that every unit was
+ * calm in the remainder launch that ended the last step, the field is a fixed point,
+ * and it stays one until somebody writes it (a load, gol_init_random, gol_write_rect,
+ * gol_snapshot_restore, a timed step, a step of fewer than tb_depth generations, a
+ * failed step: whatever withdraws gol_activity_pass_kept's record).  Until then a
+ * gol_step of at least 5 tb_depth generations replays a graph that leaves out the
+ * stencil launches from the fourth full-depth one on, which would each exit on one
+ * load, and runs one small kernel in their place; that kernel repeats their test, and
+ * if it fails the next gol_sync returns GOL_ESTATE ("short step on a field that was
+ * not still").  gol_step still returns once the work is enqueued.
+ * gol_activity_short_steps returns how many steps ran that way since create or
+ * gol_reset_timing (a host count; 0 on torus, composite, rank, group and resident
+ * engines, which never do).  The field and every other counter are what the full step
+ * leaves.  GOL_DEV_SHORT_STEP=0 at create turns it off, and so do GOL_DEV_TWIN_SURE=0
+ * and GOL_DEV_STILL_EXIT=0; GOL_DEV_SHORT_STEP=2 takes the short graph wherever the
+ * step's shape allows, seen or not (tests of the error status only). */
+gol_status gol_activity_short_steps(gol_engine* e, uint64_t* steps);
+
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */
 gol_status gol_info(gol_engine* e, uint64_t* h, uint64_t* w, uint64_t* row0,

@@ -41,6 +41,7 @@ EXPORTS = [
     "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity", "gol_plan_neighbours",
     "gol_activity_copied", "gol_activity_probed", "gol_activity_elided", "gol_torus_geometry", "gol_torus_pad",
     "gol_activity_pass_probed", "gol_plan_probe_tiles", "gol_activity_pass_kept",
+    "gol_activity_pass_sure", "gol_activity_short_steps",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
     "gol_snapshot", "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
     "gol_snapshot_drop", "gol_step_until_periodic",
@@ -230,6 +231,8 @@ def lib():
     L.gol_activity_elided.argtypes = [vp, pu64]
     L.gol_activity_pass_probed.argtypes = [vp, pu64]
     L.gol_activity_pass_kept.argtypes = [vp, pu64]
+    L.gol_activity_pass_sure.argtypes = [vp, pu64]
+    L.gol_activity_short_steps.argtypes = [vp, pu64]
     L.gol_plan_probe_tiles.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, u64,
                                        ctypes.POINTER(u32), ctypes.POINTER(u32),
                                        ctypes.POINTER(u32), pu64, pu64]
@@ -281,7 +284,8 @@ def lib():
                  "gol_plan_resident_rows", "gol_plan_exchange", "gol_activity",
                  "gol_plan_neighbours", "gol_activity_copied", "gol_activity_probed",
                  "gol_activity_elided", "gol_activity_pass_probed", "gol_plan_probe_tiles",
-                 "gol_activity_pass_kept"]:
+                 "gol_activity_pass_kept", "gol_activity_pass_sure",
+                 "gol_activity_short_steps"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -707,6 +711,21 @@ class Engine:
         already held the tile's rows (gol_activity_pass_kept)."""
         c = ctypes.c_uint64()
         _check(lib().gol_activity_pass_kept(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_pass_sure(self):
+        """Of the tile passes activity_pass_kept() counts, those that left before any
+        field load: every owner was calm in the remainder launch that ended the step
+        before (gol_activity_pass_sure)."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_pass_sure(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_short_steps(self):
+        """Steps that replayed the short graph: sync() had seen the field at a fixed
+        point and nothing wrote it since (gol_activity_short_steps; a host count)."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_short_steps(self._h, ctypes.byref(c)))
         return c.value
 
     def activity_elided(self):

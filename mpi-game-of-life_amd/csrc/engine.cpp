@@ -328,6 +328,26 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
             e->kept_tiles = (int64_t)(p0.owners.size() / gol::kCopyOwners);
             HIP_TRY(hipMalloc(&e->d_kept, (size_t)e->kept_tiles * sizeof(uint32_t)));
             HIP_TRY(hipMemsetAsync(e->d_kept, 0, (size_t)e->kept_tiles * sizeof(uint32_t), e->stream));
+            // sure tiles: a tile whose owners a remainder launch proved still leaves
+            // before its field loads (GOL_DEV_TWIN_SURE=0 = off: twin is 0 or 1 and
+            // every kept tile loads, as in r13).  One more counter word per tile.
+            const char* su = std::getenv("GOL_DEV_TWIN_SURE");
+            e->sure_on = !(su && std::atoi(su) == 0);
+            if (e->sure_on) {
+                HIP_TRY(hipMalloc(&e->d_sure, (size_t)e->kept_tiles * sizeof(uint32_t)));
+                HIP_TRY(hipMemsetAsync(e->d_sure, 0, (size_t)e->kept_tiles * sizeof(uint32_t), e->stream));
+            }
+            // short step: once gol_sync has seen every unit's twin at 2, a captured step
+            // leaves out the depth-K launches from the fourth on (GOL_DEV_SHORT_STEP=0 =
+            // off; 2 = without having seen it, for the error-code test).  It stands on
+            // the one-load exit, whose test its one node repeats, and on the 2s.
+            const char* ss = std::getenv("GOL_DEV_SHORT_STEP");
+            const int sv = ss ? std::atoi(ss) : 1;
+            e->short_on = !e->still_on ? 0 : sv == 2 ? 2 : (sv != 0 && e->sure_on) ? 1 : 0;
+            // gol_sync's look: the error word, twin[] and twin_ok, pinned
+            if (e->short_on == 1)
+                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->sync_host),
+                                      ((size_t)e->act_units + 2) * sizeof(uint32_t), hipHostMallocDefault));
         }
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -664,6 +684,11 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     // write twin[] before it; if none does, the flag goes.
     bool twin_drop = e->twin_on && e->d_streak && plan == 0;
     bool twin_last = false, twin_set = false;
+    // Sure tiles: the value the calm kernel writes for a calm unit.  2 only
+    // in the remainder branch below, where fewer than K generations have run since the
+    // streaks were written; a depth-K launch and the held writer keep 1.
+    uint32_t twin_val = 1;
+    bool short_ok = false;
     if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
         const ActState st{e->d_streak, (size_t)e->act_units};
         a.act = st.act();
@@ -692,6 +717,8 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             pass_held = e->act_probed;
             twin_drop = e->twin_on && e->act_last;
             twin_last = twin_drop && !a.no_hist;
+            // a launch the short step leaves out would have taken the one-load exit
+            short_ok = a.busy && !a.no_hist && a.launch_idx >= 3;
         } else if (may && depth < e->K && e->act_hist >= 0 && e->through_on >= 2) {
             a.streak_in = st.streak(e->act_hist);
             a.nb_off = p.d_nb;
@@ -706,6 +733,7 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             pass_all = e->act_rem > 0;
             ++e->act_rem;
             twin_last = twin_drop = e->twin_on && e->act_last;
+            if (e->sure_on) twin_val = 2;
         } else {
             e->act_hist = -1;
             e->act_probed = false;
@@ -754,6 +782,7 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         if (twin_last) {
             c.twin = st.twin();
             c.twin_ok = st.twin_ok();
+            c.twin_val = twin_val;
             twin_set = true;
         }
         HIP_TRY(gol::launch_copy_pass(c, s));
@@ -810,6 +839,7 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
             c.twin = st.twin();
             c.twin_ok = st.twin_ok();
             c.kept = e->d_kept;
+            c.sure = e->sure_on ? e->d_sure : nullptr;
         }
         HIP_TRY(gol::launch_probe_pass(c, e->rule, s));
         a.moved = st.moved();
@@ -825,7 +855,16 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
 #endif
     hipEvent_t e0, e1;
     GOL_TRY(timing_begin(e, s, &e0, &e1));
-    HIP_TRY(gol::launch_life(a, (int)depth, e->rule, e->planes, hand, s));
+    // Short step: everything around the launch has happened as in the full
+    // step, the calm kernel for twin[] before a last depth-K launch included; the
+    // stencil kernel, which would exit on one load, is left out
+    // (step_single_launches puts one node in place of all of them).
+    if (e->short_skip) {
+        if (!short_ok || e0 || s != e->stream)
+            return fail(GOL_ESTATE, "short step over a launch without the one-load exit");
+    } else {
+        HIP_TRY(gol::launch_life(a, (int)depth, e->rule, e->planes, hand, s));
+    }
     if (e0) {
         // cell-generations the lanes actually process: every stage of a block
         // computes its rows, a classic block (and the last block of a hand-off
@@ -888,6 +927,9 @@ gol_status quiesce(gol_engine* e)
 
 gol_status twin_clear(gol_engine* e, hipStream_t s)
 {
+    // (short step) whoever withdraws the record may have written the field: what
+    // gol_sync saw no longer holds, on whatever stream the write goes
+    e->still_seen = false;
     if (!e->d_streak || !e->twin_on) return GOL_OK;  // nobody reads the flag
     const ActState st{e->d_streak, (size_t)e->act_units};
     HIP_TRY(hipMemsetAsync(st.twin_ok(), 0, sizeof(uint32_t), s ? s : e->stream));
@@ -902,6 +944,13 @@ gol_status check_err(gol_engine* e)
     HIP_TRY(hipMemcpy(&err, e->d_err, sizeof(int), hipMemcpyDeviceToHost));
     if (!err) return GOL_OK;
     HIP_TRY(hipMemset(e->d_err, 0, sizeof(int)));
+    if (err == gol::kErrShortStep) {
+        // the short step's node found a unit busy in the step's third launch: the
+        // launches left out should have computed (only GOL_DEV_SHORT_STEP=2 gets here
+        // unless the host's flag was wrong)
+        (void)twin_clear(e);
+        return fail(GOL_ESTATE, "short step on a field that was not still; the field is not valid");
+    }
     for (int r = 0; r < 2; ++r)
         if (e->flags[r]) {
             const int64_t n = [&] {
@@ -1229,6 +1278,8 @@ void gol_destroy(gol_engine* e)
     if (e->mpflags) (void)hipFree(e->mpflags);
     if (e->d_streak) (void)hipFree(e->d_streak);
     if (e->d_kept) (void)hipFree(e->d_kept);
+    if (e->d_sure) (void)hipFree(e->d_sure);
+    if (e->sync_host) (void)hipHostFree(e->sync_host);
     if (e->d_err) (void)hipFree(e->d_err);
     if (e->res.flags) (void)hipFree(e->res.flags);
     for (hipEvent_t ev : {e->res.ev_in, e->res.ev_out})
@@ -1502,7 +1553,9 @@ gol_status step_single(gol_engine* e, uint64_t generations)
     e->act_probed = false;
     e->act_rem = 0;
     e->act_last = false;
+    e->twin_fresh = true;  // (short step) twin[] may change: gol_sync looks again
     const gol_status st = step_single_launches(e, generations);
+    e->short_skip = false;
     e->act_launch = -1;
     e->act_hist = -1;
     e->act_probed = false;
@@ -1517,8 +1570,18 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
 {
     uint64_t left = generations;
     const bool graphable = e->timing_every == 0 && generations >= 4 * (uint64_t)e->K;
+    // Short step: the host knows the field is a fixed point (still_seen; or
+    // GOL_DEV_SHORT_STEP=2) and the step has n >= 5 depth-K launches.  Launch 1 takes
+    // the quiet exit, launch 2 is calm, launch 3 skips on the lists and launches 4 .. n
+    // take the one-load exit: the short graph leaves those n - 3 stencil kernels out
+    // and puts one node in their place.  The graph cache's key gains the bit.
+    const uint64_t nK = generations / (uint64_t)e->K;  // pick_depth: depth K while it fits
+    const bool shorty = graphable && e->twin_on && e->still_on && e->d_streak && e->d_err &&
+                        e->plans[0].npass <= 1 && pick_depth(e->K, e->K) == e->K && nK >= 5 &&
+                        nK - 3 <= 0xFFFFFFFFull &&
+                        (e->short_on == 2 || (e->short_on == 1 && e->still_seen));
     if (graphable) {
-        const auto key = std::make_pair(generations, e->cur);
+        const auto key = std::make_pair(generations, e->cur | (shorty ? 0x100 : 0));
         auto it = e->graphs.find(key);
         if (it == e->graphs.end()) {
             if (e->graphs.size() >= kGraphCache) {
@@ -1533,13 +1596,24 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
             HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
             const int cur0 = e->cur;
             gol_status st = GOL_OK;
-            while (left > 0 && st == GOL_OK) {
+            // the host flag as it stands: nothing issued while capturing touches the field
+            const bool seen0 = e->still_seen;
+            for (uint64_t i = 0; left > 0 && st == GOL_OK; ++i) {
                 const uint32_t d = pick_depth(e->K, left);
                 const int np = passes_for(e, 0, d, left);
                 e->act_last = left == (uint64_t)d * np;
+                e->short_skip = shorty && d == e->K && i >= 3;
                 st = launch(e, 0, d, true, nullptr, np);
+                if (st == GOL_OK && e->short_skip && i == 3) {
+                    const ActState as{e->d_streak, (size_t)e->act_units};
+                    if (gol::launch_still_span(as.busy(), e->d_err, 3u, (uint32_t)(nK - 3), e->stream) !=
+                        hipSuccess)
+                        st = fail(GOL_EHIP, "short step: the span kernel did not launch");
+                }
                 left -= (uint64_t)d * np;
             }
+            e->short_skip = false;
+            e->still_seen = seen0;
             const hipError_t ce = hipStreamEndCapture(e->stream, &g);
             if (st != GOL_OK) {
                 if (g) (void)hipGraphDestroy(g);
@@ -1563,6 +1637,7 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
         it->second.used = ++e->graph_clock;
         HIP_TRY(hipGraphLaunch(it->second.exec, e->stream));
         e->cur = it->second.cur_after;
+        if (shorty) ++e->short_steps;
         return GOL_OK;
     }
     while (left > 0) {
@@ -1572,6 +1647,43 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
         GOL_TRY(launch(e, 0, d, true, nullptr, np));
         left -= (uint64_t)d * np;
     }
+    return GOL_OK;
+}
+
+// Short step, the observation: with the engine's stream idle, gol_sync
+// reads twin[] and twin_ok (they lie one after the other, act_units + 1 words) where a
+// step has run since it last looked.  twin_ok set and a 2 in every unit's word: every
+// unit was calm in the remainder launch that ended the last step, so the whole field
+// equals its generation before, and stays so until somebody writes it.  The words
+// come into pinned memory together with the error word, behind the stream's work, so
+// that gol_sync waits once and issues no blocking copy.
+static bool observe_wanted(const gol_engine* e)
+{
+    return e->short_on == 1 && e->sync_host && !e->still_seen && e->twin_fresh && e->d_streak &&
+           !e->plans.empty() && e->plans[0].total_units > 0 &&
+           e->plans[0].total_units <= e->act_units;
+}
+
+static gol_status sync_observing(gol_engine* e)
+{
+    const ActState st{e->d_streak, (size_t)e->act_units};
+    const bool look = observe_wanted(e);
+    uint32_t* host = e->sync_host;
+    host[0] = 0;
+    HIP_TRY(hipMemcpyAsync(host, e->d_err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    if (look)
+        HIP_TRY(hipMemcpyAsync(host + 1, st.twin(), (st.units + 1) * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (host[0]) return check_err(e);
+    if (!look) return GOL_OK;
+    e->twin_fresh = false;
+    const uint32_t* twin = host + 1;
+    if (twin[st.units] == 0) return GOL_OK;
+    const size_t units = (size_t)e->plans[0].total_units;
+    for (size_t u = 0; u < units; ++u)
+        if (twin[u] != 2u) return GOL_OK;
+    e->still_seen = true;
     return GOL_OK;
 }
 
@@ -1603,6 +1715,9 @@ gol_status gol_sync(gol_engine* e)
         return GOL_OK;
     }
     HIP_TRY(hipSetDevice(e->device));
+    // (short step) a single-stream engine that may arm the short graph: one wait for
+    // the work, the error word and, where a step has run, twin[]
+    if (e->sync_host && e->d_err && !e->band_stream && !e->comm_stream) return sync_observing(e);
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->band_stream) HIP_TRY(hipStreamSynchronize(e->band_stream));
     if (e->comm_stream) HIP_TRY(hipStreamSynchronize(e->comm_stream));
@@ -1873,6 +1988,7 @@ static gol_status rect_bounds(const gol_engine* e, uint64_t y, uint64_t x, uint6
 struct ActTotals {
     uint64_t computed = 0, skipped = 0, copied = 0, probed = 0, elided = 0, pass_probed = 0;
     uint64_t pass_kept = 0;  // probe-pass tiles that left their rows (gol_engine::d_kept)
+    uint64_t pass_sure = 0;  // ... of them, those that left before their field loads (d_sure)
 };
 static gol_status read_activity(gol_engine* e, ActTotals& t)
 {
@@ -1900,6 +2016,10 @@ static gol_status read_activity(gol_engine* e, ActTotals& t)
         std::vector<uint32_t> kept((size_t)e->kept_tiles);
         HIP_TRY(hipMemcpy(kept.data(), e->d_kept, kept.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (uint32_t k : kept) t.pass_kept += k;
+        if (e->d_sure) {
+            HIP_TRY(hipMemcpy(kept.data(), e->d_sure, kept.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (uint32_t k : kept) t.pass_sure += k;
+        }
     }
     return GOL_OK;
 }
@@ -2109,7 +2229,10 @@ gol_status gol_reset_timing(gol_engine* e)
         // (twin[] and twin_ok are state across steps, not statistics: left alone too)
         if (e->d_kept)
             HIP_TRY(hipMemsetAsync(e->d_kept, 0, (size_t)e->kept_tiles * sizeof(uint32_t), e->stream));
+        if (e->d_sure)
+            HIP_TRY(hipMemsetAsync(e->d_sure, 0, (size_t)e->kept_tiles * sizeof(uint32_t), e->stream));
     }
+    e->short_steps = 0;
     return GOL_OK;
 }
 
@@ -2137,6 +2260,23 @@ gol_status gol_activity_pass_kept(gol_engine* e, uint64_t* kept_tiles)
     ActTotals t;
     GOL_TRY(read_activity(e, t));
     if (kept_tiles) *kept_tiles = t.pass_kept;
+    return GOL_OK;
+}
+
+gol_status gol_activity_pass_sure(gol_engine* e, uint64_t* sure_tiles)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    ActTotals t;
+    GOL_TRY(read_activity(e, t));
+    if (sure_tiles) *sure_tiles = t.pass_sure;
+    return GOL_OK;
+}
+
+gol_status gol_activity_short_steps(gol_engine* e, uint64_t* steps)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    // a host count: torus, composite, rank, group and resident engines never arm it
+    if (steps) *steps = (e->inner || !e->parts.empty()) ? 0 : e->short_steps;
     return GOL_OK;
 }
 

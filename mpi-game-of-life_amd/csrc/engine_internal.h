@@ -79,10 +79,12 @@ struct ActState {
     uint32_t* moved() const { return base + 9 * units + 2; }
     // per unit: first launches that took it through on the probe pass's word
     uint32_t* pass_probed() const { return base + 10 * units + 2; }
-    // per unit: 1 = both field buffers hold the unit's rows, word for word, as the
+    // per unit: 1 or 2 = both field buffers hold the unit's rows, word for word, as the
     // step's last launch left them (life_copy.hip writes it, life_probe.hip reads it in
     // the next step); it says so only while *twin_ok is 1, which every other writer
-    // of the field clears (DESIGN §4 "Probe pass: rows both buffers hold")
+    // of the field clears (DESIGN §4 "Probe pass: rows both buffers hold"); 2 = written
+    // before a remainder launch: the unit's rows also keep their state for one more
+    // generation (DESIGN §4 "Sure tiles")
     uint32_t* twin() const { return base + 11 * units + 2; }
     uint32_t* twin_ok() const { return base + 12 * units + 2; }
     size_t words() const { return 12 * units + 3; }
@@ -403,6 +405,27 @@ struct gol_engine {
     // per tile of plan 0's probe pass: passes that left the tile's rows unstored
     uint32_t* d_kept = nullptr;
     int64_t kept_tiles = 0;
+    // sure tiles: a remainder launch that ends a step writes twin = 2, and a tile of
+    // the next probe pass whose owners all have it leaves before its field loads
+    // (GOL_DEV_TWIN_SURE=0 turns it off; only with twin_on).  d_sure: per tile, the
+    // passes in which it left so (kept_tiles words).
+    bool sure_on = false;
+    uint32_t* d_sure = nullptr;
+    // Short step: gol_sync found twin_ok set and every unit's twin 2, so
+    // the field is a fixed point, and nobody has written it since (twin_clear withdraws
+    // the flag, on whatever stream it is called).  A captured step of 5 or more depth-K
+    // launches then replays a graph without the stencil kernels of launches 4 .. n.
+    // short_on: GOL_DEV_SHORT_STEP, 0 = off, 1 = on (needs sure_on, the only writer of
+    // 2), 2 = take the short graph wherever the shape allows (the error-code test).
+    // twin_fresh: a step ran since gol_sync last read twin[] (into sync_host);
+    // short_skip: launch() does everything but enqueue the stencil kernel; short_steps: steps that replayed
+    // a short graph (gol_activity_short_steps).
+    int short_on = 0;
+    bool still_seen = false;
+    bool twin_fresh = false;
+    bool short_skip = false;
+    uint64_t short_steps = 0;
+    uint32_t* sync_host = nullptr;  // pinned, act_units + 2 words: d_err, twin[], twin_ok
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on

@@ -56,9 +56,10 @@ __global__ __launch_bounds__(256) void life_calm_kernel(CopyArgs a)
         // Rows both buffers hold: before a step's last launch.  A calm unit's
         // output rows equal its input rows, however they get there, and the launch's
         // input buffer is the other one once the step has ended.  A unit that computes
-        // gets 0, quiet or not.
+        // gets 0, quiet or not.  twin_val: 2 before a remainder launch, whose calm units
+        // are still one generation on as well (DESIGN §4 "Sure tiles"), else 1.
         if (a.twin) {
-            a.twin[unit] = calm ? 1u : 0u;
+            a.twin[unit] = calm ? (a.twin_val == 2u ? 2u : 1u) : 0u;
             if (unit == 0) *a.twin_ok = 1u;
         }
         if (!a.need) return;
@@ -79,6 +80,21 @@ __global__ __launch_bounds__(256) void life_twin_held_kernel(const uint32_t* hel
     if (u >= (uint32_t)units) return;
     twin[u] = held[u] != 0u ? 1u : 0u;
     if (u == 0) *twin_ok = 1u;
+}
+
+// The short step's one node (DESIGN §4 "Short step"): stands for `count` depth-K launches
+// from index first_idx on, each of which would take the one-load exit
+// (life_stencil.h: busy[1] < launch_idx, none of them writes busy[1]) and add 1 to
+// busy[0].  The same test; where it fails the replacement is not exact, the launches
+// left out should have computed, and the next gol_sync reports it.
+__global__ __launch_bounds__(64) void life_still_span_kernel(uint32_t* busy, int* err,
+                                                             uint32_t first_idx, uint32_t count)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (busy[1] < first_idx)
+        busy[0] += count;
+    else
+        *err = kErrShortStep;
 }
 
 // One wavefront per tile of kCopyTileRows rows x kCopyTileWords words, lane l = word
@@ -150,6 +166,14 @@ hipError_t launch_twin_held(const uint32_t* held, uint32_t* twin, uint32_t* twin
     if (units <= 0 || !held || !twin || !twin_ok) return hipErrorInvalidValue;
     hipLaunchKernelGGL(life_twin_held_kernel, dim3(((unsigned)units + 255) / 256), dim3(256), 0, s,
                        held, twin, twin_ok, units);
+    return hipGetLastError();
+}
+
+hipError_t launch_still_span(uint32_t* busy, int* err, uint32_t first_idx, uint32_t count,
+                             hipStream_t s)
+{
+    if (!busy || !err || count == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(life_still_span_kernel, dim3(1), dim3(64), 0, s, busy, err, first_idx, count);
     return hipGetLastError();
 }
 

@@ -276,6 +276,10 @@ struct CopyArgs {
     // `need` null it writes nothing else (launch_twin_flags).
     uint32_t* twin;
     uint32_t* twin_ok;
+    // Sure tiles: the value a calm unit's twin word gets.  2 only before a
+    // remainder launch (fewer than K generations run since the streaks were written);
+    // anything else writes 1.
+    uint32_t twin_val;
 };
 hipError_t launch_copy_pass(const CopyArgs& a, hipStream_t s);
 // The pass's first kernel alone, for twin[] only (need and elided null): before a
@@ -285,6 +289,14 @@ hipError_t launch_twin_flags(const CopyArgs& a, hipStream_t s);
 // that launch probed and wrote held[] for every unit.
 hipError_t launch_twin_held(const uint32_t* held, uint32_t* twin, uint32_t* twin_ok, int32_t units,
                             hipStream_t s);
+// The short step (DESIGN §4 "Short step"): one wavefront in place of `count` depth-K
+// launches of a step, the first of them with StepArgs::launch_idx = first_idx, that
+// would all take the one-load exit: busy[1] < first_idx adds count to busy[0], anything
+// else stores kErrShortStep to *err (the engine's error word; the kernels' wait
+// timeouts store 1).
+constexpr int kErrShortStep = 2;
+hipError_t launch_still_span(uint32_t* busy, int* err, uint32_t first_idx, uint32_t count,
+                             hipStream_t s);
 
 // The probe pass (life_probe.hip, DESIGN §4 "Probe pass"): one generation over the
 // copy pass's tiles before a step's first launch, in the copy pass's shape.  A device
@@ -316,6 +328,10 @@ struct ProbeArgs {
     const uint32_t* twin;
     const uint32_t* twin_ok;
     uint32_t* kept;  // ntile words
+    // Sure tiles (set with the four above, or null): a tile that would be
+    // kept and whose owners' twin words are all 2 is proven to keep its state for one
+    // generation, so it counts in kept[tile] and in sure[tile] before any field load.
+    uint32_t* sure;  // ntile words
 };
 hipError_t launch_probe_pass(const ProbeArgs& a, RuleKind rule, hipStream_t s);
 

@@ -20,6 +20,11 @@
 // the step before recorded per unit (ActState::twin, valid while twin_ok is set).
 // "Stored its rows" above then reads "the destination holds its rows": the same
 // content, so everything that follows from it stands.
+//
+// Sure tiles: where that last launch was a remainder launch, its calm units
+// got twin = 2, and a tile all of whose owners have it keeps its state for one
+// generation by proof.  It ends as the twin tile it would turn out to be, before its
+// field loads, and counts in sure[tile] as well.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,8 +43,8 @@ __global__ __launch_bounds__(256) void life_probe_zero_kernel(uint32_t* moved, i
 
 // Lane l = word l of the tile's column segment, consecutive tiles along a row chunk.
 // Every index is checked against the table's and the plan's bounds before any access.
-// (8 wavefronts per SIMD, the copy kernel's occupancy: at most 64 registers, 50 used.
-// The generic rule's 10-term mask sum spills at 64 and at 80: it stays uncapped, 95
+// (8 wavefronts per SIMD, the copy kernel's occupancy: at most 64 registers, 52 used.
+// The generic rule's 10-term mask sum spills at 64 and at 80: it stays uncapped, 96
 // registers, 5 wavefronts per SIMD, no scratch.)
 template <int RULE>
 __global__ __launch_bounds__(256, RULE == RULE_GENERIC ? 1 : 8) void life_probe_kernel(ProbeArgs a)
@@ -77,6 +82,17 @@ __global__ __launch_bounds__(256, RULE == RULE_GENERIC ? 1 : 8) void life_probe_
     const uint32_t tw_ok = a.twin ? *a.twin_ok : 0u;
     const bool twin_tile = tw_ok != 0u && __builtin_amdgcn_ballot_w64(owned) != 0 &&
                            __builtin_amdgcn_ballot_w64(tw == 0u) == 0;
+    // Sure tiles: every owner was calm in a remainder launch that ended the
+    // step before, so generation 1 equals the input on every word of the tile: the
+    // loads below would find diff == 0 and the tile would end as a twin tile.  It ends
+    // so here, leaving moved[], kept[] and the field as that path leaves them.
+    if (a.sure && twin_tile && __builtin_amdgcn_ballot_w64(owned && tw != 2u) == 0) {
+        if (lane == 0) {
+            a.kept[tile] += 1u;
+            a.sure[tile] += 1u;
+        }
+        return;
+    }
     {
         const uint32_t m = listed ? __hip_atomic_load(a.moved + unit, __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_AGENT)

@@ -113,6 +113,13 @@ gol_status torus_create(uint64_t h, uint64_t w, const gol_config* cfg, gol_engin
         delete e;
         return fail(GOL_ESTATE, "torus: unexpected inner engine layout");
     }
+    // (short step) the wrap withdraws the record before every round: the
+    // inner engine's gol_sync has nothing to look for
+    e->inner->short_on = 0;
+    if (e->inner->sync_host) {
+        (void)hipHostFree(e->inner->sync_host);
+        e->inner->sync_host = nullptr;
+    }
     e->sem = GOL_SEM_TORUS;
     e->H = e->R = h;
     e->W = w;

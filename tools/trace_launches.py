@@ -9,7 +9,9 @@ life_probe_zero_kernel and life_probe_kernel precede launch 1.  Medians over the
 (the still probe), the pass and launch 2 (each, and from the pass's start to the
 launch's end),
 launch 3 (skips by its lists), launches 4-62 (the one-load exit; duration and pitch),
-the remainder likewise, and the step's span.
+the remainder likewise, and the step's span.  A short step (DESIGN §4 "Short step")
+has three depth-16 launches and life_still_span_kernel in place of the others: its
+duration is still_span_us, and launches_per_step counts every kernel of the step.
 
     python tools/trace_launches.py TRACE_kernel_trace.csv [--steps 20] [--depth 16]
 """
@@ -35,7 +37,8 @@ def main():
     for r in csv.DictReader(open(a.trace)):
         name = r["Kernel_Name"]
         kind = ("copy" if ("life_copy_kernel" in name or "life_calm_kernel" in name)
-                else "probe" if "life_probe_" in name else depth_of(name))
+                else "probe" if "life_probe_" in name
+                else "span" if "life_still_span_kernel" in name else depth_of(name))
         if kind is not None:
             ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), kind))
     ev.sort()
@@ -43,10 +46,11 @@ def main():
     steps, cur = [], []
     for s, e, kind in ev:
         cur.append((s, e, kind))
-        if kind not in ("copy", "probe") and kind != a.depth:
+        if kind not in ("copy", "probe", "span") and kind != a.depth:
             steps.append(cur)
             cur = []
-    full = [st for st in steps if sum(1 for x in st if x[2] == a.depth) >= 4][-a.steps:]
+    full = [st for st in steps if sum(1 for x in st if x[2] == a.depth) >= 4
+            or (any(x[2] == "span" for x in st) and sum(1 for x in st if x[2] == a.depth) == 3)][-a.steps:]
     cols = {}
 
     def add(key, ns):
@@ -68,6 +72,9 @@ def main():
             add("launch4_on_us", x[1] - x[0])
             add("launch4_on_pitch_us", y[0] - x[0])
         add("remainder_us", rem[1] - rem[0])
+        for x in st:
+            if x[2] == "span":
+                add("still_span_us", x[1] - x[0])
         p2 = [c for c in copies if deep[0][1] <= c[0] <= deep[1][0]]
         pr = [c for c in copies if deep[-1][1] <= c[0] <= rem[0]]
         if p2:
