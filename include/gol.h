@@ -307,6 +307,44 @@ gol_status gol_activity_pass_sure(gol_engine* e, uint64_t* sure_tiles);
  * step's shape allows, seen or not (tests of the error status only). */
 gol_status gol_activity_short_steps(gol_engine* e, uint64_t* steps);
 
+/* Fixed step (DESIGN.md section 4 "Fixed step").  Where the short step's conditions
+ * hold and the host also knows that the last step ended with a remainder launch that
+ * found every unit calm (gol_sync saw a 2 in every unit's word, and every step since
+ * kept it), a gol_step is one small kernel, launched directly: it repeats that test on
+ * the device and then leaves the activity state and the counters word for word as the
+ * step's kernels would.  Where the test fails it writes nothing, and the next gol_sync
+ * returns GOL_ESTATE as for the short step.
+ * gol_plan_still_step (host only, no GPU) returns what such a step of `generations`
+ * generations at depth tb_depth does to the activity state: increments of the
+ * counters, final values of the state words (none of which depends on what the word
+ * held before), and how many probe passes count every owned tile.  GOL_EINVAL where
+ * the step has fewer than 5 full-depth launches or tb_depth is no kernel depth.
+ * gol_activity_fixed_steps: steps that ran so since create or gol_reset_timing (a host
+ * count; they count in gol_activity_short_steps as well).  GOL_DEV_FIXED_STEP=0 at
+ * create turns the path off (the short graph runs instead), as does whatever turns
+ * the short step off; GOL_DEV_FIXED_STEP=2 takes it after every step that ended with
+ * a remainder launch, seen or not (tests of the error status only). */
+typedef struct gol_still_effect {
+    uint64_t launches;    /* stencil launches the step stands for (the buffers swap per launch) */
+    /* added to every unit's counter */
+    uint32_t computed, skipped, copied, probed, pass_probed, elided;
+    uint32_t busy0_add;   /* added to the count of launches that every unit skipped */
+    /* final values */
+    uint32_t busy1;       /* index + 1 of the last launch in which a unit stored rows */
+    uint32_t streak0, streak1, need, held, moved, twin; /* per unit */
+    uint32_t twin_ok;
+    uint32_t kept_passes, sure_passes; /* probe passes that count every owned tile */
+} gol_still_effect;
+gol_status gol_plan_still_step(uint32_t tb_depth, uint64_t generations, gol_still_effect* out);
+gol_status gol_activity_fixed_steps(gol_engine* e, uint64_t* steps);
+
+/* The activity state as it lies on the device, after everything enqueued has run:
+ * 12 * units + 3 words (engine_internal.h ActState names the regions), for tests that
+ * compare two engines word for word.  *words receives the count; the words are copied
+ * where cap holds them all, else GOL_EINVAL.  GOL_ESTATE: the engine keeps no activity
+ * state (torus, composite, rank, group and resident engines). */
+gol_status gol_activity_state(gol_engine* e, uint32_t* out, size_t cap, size_t* words);
+
 /* Engine geometry as chosen (for tools / tests); any out pointer may be NULL.
  * rows_per_wave: the rows each wavefront streams in a full-depth launch. */
 gol_status gol_info(gol_engine* e, uint64_t* h, uint64_t* w, uint64_t* row0,

@@ -42,6 +42,7 @@ EXPORTS = [
     "gol_activity_copied", "gol_activity_probed", "gol_activity_elided", "gol_torus_geometry", "gol_torus_pad",
     "gol_activity_pass_probed", "gol_plan_probe_tiles", "gol_activity_pass_kept",
     "gol_activity_pass_sure", "gol_activity_short_steps",
+    "gol_plan_still_step", "gol_activity_fixed_steps", "gol_activity_state",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
     "gol_snapshot", "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
     "gol_snapshot_drop", "gol_step_until_periodic",
@@ -114,6 +115,14 @@ class PlanSummary(ctypes.Structure):
         ("handoff", ctypes.c_int32), ("tail_off", ctypes.c_int32),
         ("candidates", ctypes.c_uint32), ("passes", ctypes.c_uint32),
     ]
+
+
+class StillEffect(ctypes.Structure):
+    """gol_still_effect: what a step on a proven fixed point does to the activity state."""
+    _fields_ = [("launches", ctypes.c_uint64)] + [(k, ctypes.c_uint32) for k in (
+        "computed", "skipped", "copied", "probed", "pass_probed", "elided", "busy0_add",
+        "busy1", "streak0", "streak1", "need", "held", "moved", "twin", "twin_ok",
+        "kept_passes", "sure_passes")]
 
 
 class Until(ctypes.Structure):
@@ -233,6 +242,9 @@ def lib():
     L.gol_activity_pass_kept.argtypes = [vp, pu64]
     L.gol_activity_pass_sure.argtypes = [vp, pu64]
     L.gol_activity_short_steps.argtypes = [vp, pu64]
+    L.gol_activity_fixed_steps.argtypes = [vp, pu64]
+    L.gol_activity_state.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.gol_plan_still_step.argtypes = [u32, u64, ctypes.POINTER(StillEffect)]
     L.gol_plan_probe_tiles.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, u64,
                                        ctypes.POINTER(u32), ctypes.POINTER(u32),
                                        ctypes.POINTER(u32), pu64, pu64]
@@ -285,7 +297,8 @@ def lib():
                  "gol_plan_neighbours", "gol_activity_copied", "gol_activity_probed",
                  "gol_activity_elided", "gol_activity_pass_probed", "gol_plan_probe_tiles",
                  "gol_activity_pass_kept", "gol_activity_pass_sure",
-                 "gol_activity_short_steps"]:
+                 "gol_activity_short_steps", "gol_plan_still_step",
+                 "gol_activity_fixed_steps", "gol_activity_state"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -351,6 +364,15 @@ def plan_model(h, w, rank=0, nranks=1, cus=256, occ_classic=2, occ_hand=2, **cfg
     _check(lib().gol_plan_model(h, w, ctypes.byref(cfg), rank, nranks, cus, occ_classic,
                                 occ_hand, ctypes.byref(out)))
     return {k: getattr(out, k) for k, _ in PlanSummary._fields_ if k != "reserved"}
+
+
+def plan_still_step(tb_depth, generations):
+    """gol_plan_still_step (host only, no GPU): what a gol_step of `generations`
+    generations at depth `tb_depth` does to the activity state of a field that is a
+    proven fixed point (DESIGN §4 "Fixed step").  Returns a dict of StillEffect."""
+    out = StillEffect()
+    _check(lib().gol_plan_still_step(tb_depth, generations, ctypes.byref(out)))
+    return {k: getattr(out, k) for k, _ in StillEffect._fields_}
 
 
 def plan_neighbours(h, w, cus=256, occ_classic=2, occ_hand=2, **cfg_kw):
@@ -727,6 +749,24 @@ class Engine:
         c = ctypes.c_uint64()
         _check(lib().gol_activity_short_steps(self._h, ctypes.byref(c)))
         return c.value
+
+    def activity_fixed_steps(self):
+        """Of the steps activity_short_steps() counts, those that ran as one kernel: the
+        host also knew that the step before had ended with a remainder launch that found
+        every unit calm (gol_activity_fixed_steps; a host count)."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_fixed_steps(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_state(self):
+        """The activity state's words as they lie on the device, after everything
+        enqueued has run (gol_activity_state): a uint32 array of 12 * units + 3."""
+        import numpy as np
+        n = ctypes.c_size_t()
+        _check(lib().gol_activity_state(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        _check(lib().gol_activity_state(self._h, out.ctypes.data, out.size, ctypes.byref(n)))
+        return out
 
     def activity_elided(self):
         """Calm units whose rows the copy pass left alone because its destination

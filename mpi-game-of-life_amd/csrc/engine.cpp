@@ -348,6 +348,45 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
             if (e->short_on == 1)
                 HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->sync_host),
                                       ((size_t)e->act_units + 2) * sizeof(uint32_t), hipHostMallocDefault));
+            // fixed step: one kernel for the whole step (GOL_DEV_FIXED_STEP=0 = off; 2 =
+            // unseen, for the error-status test).  It stands for the kernels of a step
+            // in which every one of these is on, over a plan whose launches all track
+            // activity, whose units all own rows and whose tiles all have an owner:
+            // anything else keeps the short graph.
+            const char* fx = std::getenv("GOL_DEV_FIXED_STEP");
+            const int fv = fx ? std::atoi(fx) : 1;
+            bool whole = e->short_on != 0 && e->through_on >= 2 && e->elide_on && e->sure_on &&
+                         e->nbuf == 2 && !e->xcd_shift && e->nranks <= 1 && p0.segs.size() == 1 &&
+                         p0.npass == 1 && p0.d_nb && p0.total_units > 0 &&
+                         p0.total_units <= e->act_units && p0.total_units <= 0xFFFFFFFFll;
+            // no launch of the step runs hand-off row blocks (launch(): such a launch
+            // leaves the activity state alone)
+            for (int d : gol::kDepthList)
+                if ((uint32_t)d <= e->K && p0.hand && p0.multi_blk && e->side[0] &&
+                    handoff_fits(p0.rpw, d, e->planes) && gol::handoff_kernel_exists(d, e->rule))
+                    whole = false;
+            if (whole) {
+                // every unit owns rows (life_stencil.h: a unit without rows neither
+                // probes nor writes held = 1) ...
+                std::vector<URect> rc;
+                unit_rects(p0, (int64_t)e->ng, rc);
+                for (int64_t u = 0; u < p0.total_units; ++u)
+                    if (rc[(size_t)(2 * u)].r1 <= rc[(size_t)(2 * u)].r0) whole = false;
+                // ... and every tile with a row has an owner (life_probe.hip: a tile
+                // without one is no twin tile, and would load and store its rows)
+                const SegDesc& sg = p0.segs[0];
+                int64_t owned = 0;
+                for (int64_t t = 0; t < e->kept_tiles; ++t) {
+                    const int64_t rb = sg.out_lo + t / p0.copy_ncol * gol::kCopyTileRows;
+                    bool own = false;
+                    for (int k = 0; k < gol::kCopyOwners; ++k)
+                        own = own || (int64_t)p0.owners[(size_t)(t * gol::kCopyOwners + k)] < p0.total_units;
+                    if (rb >= 0 && rb < sg.out_hi && own) ++owned;
+                }
+                e->owned_tiles = owned;
+                if (sg.out_lo < 0 || owned != e->kept_tiles) whole = false;
+            }
+            e->fixed_on = !whole ? 0 : fv == 2 ? 2 : (fv != 0 && e->short_on == 1) ? 1 : 0;
         }
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -930,6 +969,7 @@ gol_status twin_clear(gol_engine* e, hipStream_t s)
     // (short step) whoever withdraws the record may have written the field: what
     // gol_sync saw no longer holds, on whatever stream the write goes
     e->still_seen = false;
+    e->twin_two = false;  // (fixed step) twin[] says nothing any more
     if (!e->d_streak || !e->twin_on) return GOL_OK;  // nobody reads the flag
     const ActState st{e->d_streak, (size_t)e->act_units};
     HIP_TRY(hipMemsetAsync(st.twin_ok(), 0, sizeof(uint32_t), s ? s : e->stream));
@@ -949,6 +989,7 @@ gol_status check_err(gol_engine* e)
         // launches left out should have computed (only GOL_DEV_SHORT_STEP=2 gets here
         // unless the host's flag was wrong)
         (void)twin_clear(e);
+        e->rem_ended = false;
         return fail(GOL_ESTATE, "short step on a field that was not still; the field is not valid");
     }
     for (int r = 0; r < 2; ++r)
@@ -1538,6 +1579,107 @@ int passes_for(const gol_engine* e, int plan, uint32_t d, uint64_t left)
     return (int)std::min<uint64_t>((uint64_t)np, left / d);
 }
 
+// Fixed step: what a step of `generations` generations at depth K does to
+// the activity state when it starts with twin_ok == 1 and twin[u] == 2 for every unit,
+// every switch of the activity skip on.  The loop is step_single_launches' (pick_depth,
+// act_last), the branches are launch()'s; every unit goes the same way through every
+// kernel, so one record serves all of them.  False: not a short step's shape.
+static bool still_effect(uint32_t K, uint64_t generations, gol_still_effect* out)
+{
+    gol_still_effect fx{};
+    if (K == 0 || pick_depth(K, K) != K) return false;
+    const uint64_t nK = generations / K;
+    if (nK < 5 || nK - 3 > 0xFFFFFFFFull) return false;
+    uint64_t left = generations;
+    int hist = -1;  // launch(): act_hist, the streak parity the last depth-K launch wrote
+    for (uint64_t i = 0; left > 0; ++i) {
+        const uint32_t d = pick_depth(K, left);
+        const bool last = left == d;  // act_last (one pass per launch)
+        if (d == K && i == 0) {
+            // First launch: no history, it probes.  The probe pass before it zeroes
+            // moved[] (life_probe.hip life_probe_zero_kernel); every owned tile has
+            // owners with twin == 2 under twin_ok and takes the sure-tile exit, which
+            // adds 1 to kept[tile] and to sure[tile] and touches nothing else
+            // (life_probe.hip:89-95), so moved[] stays 0.
+            fx.moved = 0;
+            fx.kept_passes += 1;
+            fx.sure_passes += 1;
+            // The launch: every unit that goes on writes busy[1] = launch_idx + 1 = 1
+            // (life_stencil.h:564), finds moved[unit] == 0 and takes the quiet exit
+            // (:902-908): streak_out = min(0 + 1, cap) in streak(1), computed, probed
+            // and pass_probed + 1, held = 1.
+            fx.busy1 = 1;
+            fx.streak1 = 1;
+            fx.computed += 1;
+            fx.probed += 1;
+            fx.pass_probed += 1;
+            fx.held = 1;
+            hist = 1;
+        } else if (d == K && i == 1) {
+            // Second launch, behind the copy pass.  life_calm_kernel: every list entry
+            // has streak(1) == 1, so calm and not still; held[unit] is 1, so the
+            // destination holds the rows: need = 0, elided + 1.  No tile has need: the
+            // tile kernel writes nothing.  The launch: busy[1] == 1 is not below its
+            // index, the lists say calm, not still: busy[1] = 2 (:564) and the
+            // copy-through exit with `through` == 2 (:844-846): streak_out = 1 + 1 in
+            // streak(0), computed + 1, copied + 1.
+            fx.need = 0;
+            fx.elided += 1;
+            fx.busy1 = 2;
+            fx.streak0 = 2;
+            fx.computed += 1;
+            fx.copied += 1;
+            hist = 0;
+        } else if (d == K && i == 2) {
+            // Third launch: busy[1] == 2 is not below 2; every list entry has
+            // streak(0) == 2: the unit skips (:555-560), streak_out = 2 + 1 in
+            // streak(1), skipped + 1.  Nobody writes busy[1].
+            fx.streak1 = 3;
+            fx.skipped += 1;
+            hist = 1;
+        } else if (d == K) {
+            // Launches 4 .. n: busy[1] == 2 < launch_idx >= 3, the one-load exit
+            // (:540-543): busy[0] + 1, no streak written (the short graph's span kernel
+            // adds them up in one go).  launch() still alternates the parity.
+            // All of them at once.
+            const uint64_t more = nK - 1 - i;
+            fx.busy0_add += (uint32_t)(more + 1);
+            fx.launches += more;
+            left -= more * K;
+            i += more;
+            hist = (int)(i & 1) ^ 1;
+            // the step's last launch: life_calm_kernel alone (launch_twin_flags), calm
+            // on streaks of 2 or 3, twin_val 1
+            if (left == K) {
+                fx.twin = 1;
+                fx.twin_ok = 1;
+            }
+        } else {
+            // A remainder launch, behind the copy pass on the streaks `hist` names (2
+            // or 3 everywhere).  life_calm_kernel: calm and still, so need = 0 and
+            // elided + 1 (from the second remainder launch on all_held says the same
+            // and the tile kernel is left out); before the step's last launch twin = 2
+            // (sure tiles) and twin_ok = 1.  The launch has no busy[] and no
+            // streak_out: it neither takes the one-load exit nor skips, and every
+            // unit copies through with `through` == 2 (:844-846): computed + 1,
+            // copied + 1, no streak written.
+            if (hist < 0) return false;
+            fx.need = 0;
+            fx.elided += 1;
+            fx.computed += 1;
+            fx.copied += 1;
+            if (last) {
+                fx.twin = 2;
+                fx.twin_ok = 1;
+            }
+        }
+        fx.launches += 1;
+        left -= d;
+    }
+    *out = fx;
+    return true;
+}
+
 // Single-stream engines: the launch sequence of gol_step(gens) as a captured
 // hipGraph, replayed from the second call on (LRU cache keyed by gens and the
 // starting buffer).
@@ -1563,6 +1705,8 @@ gol_status step_single(gol_engine* e, uint64_t generations)
     e->act_last = false;
     // a step that failed half-way leaves no statement about the buffers
     if (st != GOL_OK) (void)twin_clear(e);
+    // (fixed step, GOL_DEV_FIXED_STEP=2) depth-K launches, then a remainder launch
+    e->rem_ended = st == GOL_OK && generations > (uint64_t)e->K && generations % (uint64_t)e->K != 0;
     return st;
 }
 
@@ -1580,6 +1724,62 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
                         e->plans[0].npass <= 1 && pick_depth(e->K, e->K) == e->K && nK >= 5 &&
                         nK - 3 <= 0xFFFFFFFFull &&
                         (e->short_on == 2 || (e->short_on == 1 && e->still_seen));
+    // Fixed step: the short step's conditions (but for its unseen mode), and
+    // the host knows that twin[] holds 2.  One kernel, launched directly: no capture,
+    // no graph.  It repeats the proof on the device; where that fails it writes
+    // nothing but the error word, and the next gol_sync reports it (check_err).
+    const bool shape = graphable && e->fixed_on && e->twin_on && e->still_on && e->d_streak &&
+                       e->d_err && e->plans[0].npass <= 1 && nK >= 5 && nK - 3 <= 0xFFFFFFFFull;
+    if (shape && ((e->fixed_on == 1 && e->short_on == 1 && e->still_seen && e->twin_two) ||
+                  (e->fixed_on == 2 && e->rem_ended))) {
+        gol_still_effect fx;
+        if (!still_effect(e->K, generations, &fx))
+            return fail(GOL_ESTATE, "fixed step: not a short step's shape");
+        const ActState st{e->d_streak, (size_t)e->act_units};
+        gol::StillArgs a{};
+        a.streak0 = st.streak(0);
+        a.streak1 = st.streak(1);
+        a.act = st.act();
+        a.copied = st.copied();
+        a.busy = st.busy();
+        a.probed = st.probed();
+        a.need = st.need();
+        a.held = st.held();
+        a.elided = st.elided();
+        a.moved = st.moved();
+        a.pass_probed = st.pass_probed();
+        a.twin = st.twin();
+        a.twin_ok = st.twin_ok();
+        a.err = e->d_err;
+        a.total_units = (uint32_t)e->plans[0].total_units;
+        a.act_units = (uint32_t)std::min<int64_t>(e->act_units, 0xFFFFFFFFll);
+        a.computed = fx.computed;
+        a.skipped = fx.skipped;
+        a.n_copied = fx.copied;
+        a.n_probed = fx.probed;
+        a.n_pass_probed = fx.pass_probed;
+        a.n_elided = fx.elided;
+        a.busy0_add = fx.busy0_add;
+        a.busy1 = fx.busy1;
+        a.v_streak0 = fx.streak0;
+        a.v_streak1 = fx.streak1;
+        a.v_need = fx.need;
+        a.v_held = fx.held;
+        a.v_moved = fx.moved;
+        a.v_twin = fx.twin;
+        a.v_twin_ok = fx.twin_ok;
+        HIP_TRY(gol::launch_still_step(a, e->stream));
+        // every launch swaps the buffers, which hold the same field
+        e->cur = (int)(((uint64_t)e->cur + fx.launches) % (uint64_t)e->nbuf);
+        ++e->short_steps;
+        ++e->fixed_steps;
+        e->fixed_passes += fx.kept_passes;  // (= sure_passes: one probe pass, all sure)
+        e->twin_two = e->twin_two && fx.twin == 2;
+        return GOL_OK;
+    }
+    // any other step keeps the host's word on twin[] only where it replays a short graph
+    // that ends with a remainder launch, which writes the 2s again
+    e->twin_two = e->twin_two && shorty && generations % (uint64_t)e->K != 0;
     if (graphable) {
         const auto key = std::make_pair(generations, e->cur | (shorty ? 0x100 : 0));
         auto it = e->graphs.find(key);
@@ -1597,7 +1797,7 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
             const int cur0 = e->cur;
             gol_status st = GOL_OK;
             // the host flag as it stands: nothing issued while capturing touches the field
-            const bool seen0 = e->still_seen;
+            const bool seen0 = e->still_seen, two0 = e->twin_two;
             for (uint64_t i = 0; left > 0 && st == GOL_OK; ++i) {
                 const uint32_t d = pick_depth(e->K, left);
                 const int np = passes_for(e, 0, d, left);
@@ -1614,6 +1814,7 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
             }
             e->short_skip = false;
             e->still_seen = seen0;
+            e->twin_two = two0;
             const hipError_t ce = hipStreamEndCapture(e->stream, &g);
             if (st != GOL_OK) {
                 if (g) (void)hipGraphDestroy(g);
@@ -1659,7 +1860,9 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
 // that gol_sync waits once and issues no blocking copy.
 static bool observe_wanted(const gol_engine* e)
 {
-    return e->short_on == 1 && e->sync_host && !e->still_seen && e->twin_fresh && e->d_streak &&
+    // (fixed step) ... and where the field is known still but not that twin[] holds 2
+    const bool news = !e->still_seen || (e->fixed_on == 1 && !e->twin_two);
+    return e->short_on == 1 && e->sync_host && news && e->twin_fresh && e->d_streak &&
            !e->plans.empty() && e->plans[0].total_units > 0 &&
            e->plans[0].total_units <= e->act_units;
 }
@@ -1684,6 +1887,7 @@ static gol_status sync_observing(gol_engine* e)
     for (size_t u = 0; u < units; ++u)
         if (twin[u] != 2u) return GOL_OK;
     e->still_seen = true;
+    e->twin_two = true;  // (fixed step) until a step ends with a depth-K launch
     return GOL_OK;
 }
 
@@ -2021,6 +2225,10 @@ static gol_status read_activity(gol_engine* e, ActTotals& t)
             for (uint32_t k : kept) t.pass_sure += k;
         }
     }
+    // (fixed step) its probe passes, each of which would have counted every owned tile
+    // in both arrays
+    t.pass_kept += e->fixed_passes * (uint64_t)e->owned_tiles;
+    if (e->d_sure) t.pass_sure += e->fixed_passes * (uint64_t)e->owned_tiles;
     return GOL_OK;
 }
 
@@ -2233,6 +2441,8 @@ gol_status gol_reset_timing(gol_engine* e)
             HIP_TRY(hipMemsetAsync(e->d_sure, 0, (size_t)e->kept_tiles * sizeof(uint32_t), e->stream));
     }
     e->short_steps = 0;
+    e->fixed_steps = 0;
+    e->fixed_passes = 0;
     return GOL_OK;
 }
 
@@ -2277,6 +2487,37 @@ gol_status gol_activity_short_steps(gol_engine* e, uint64_t* steps)
     if (!e) return fail(GOL_EINVAL, "null engine");
     // a host count: torus, composite, rank, group and resident engines never arm it
     if (steps) *steps = (e->inner || !e->parts.empty()) ? 0 : e->short_steps;
+    return GOL_OK;
+}
+
+gol_status gol_activity_fixed_steps(gol_engine* e, uint64_t* steps)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    // a host count, as gol_activity_short_steps
+    if (steps) *steps = (e->inner || !e->parts.empty()) ? 0 : e->fixed_steps;
+    return GOL_OK;
+}
+
+gol_status gol_activity_state(gol_engine* e, uint32_t* out, size_t cap, size_t* words)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    if (e->inner || !e->parts.empty() || !e->d_streak)
+        return fail(GOL_ESTATE, "the engine keeps no activity state");
+    const ActState dev{e->d_streak, (size_t)e->act_units};
+    if (words) *words = dev.words();
+    if (!out) return GOL_OK;
+    if (cap < dev.words()) return fail(GOL_EINVAL, "activity state: the buffer is too small");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(out, dev.base, dev.words() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return GOL_OK;
+}
+
+gol_status gol_plan_still_step(uint32_t tb_depth, uint64_t generations, gol_still_effect* out)
+{
+    if (!out) return fail(GOL_EINVAL, "null argument");
+    if (!still_effect(tb_depth, generations, out))
+        return fail(GOL_EINVAL, "not a short step: fewer than 5 launches of a kernel depth");
     return GOL_OK;
 }
 

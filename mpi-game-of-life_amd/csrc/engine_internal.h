@@ -426,6 +426,24 @@ struct gol_engine {
     bool short_skip = false;
     uint64_t short_steps = 0;
     uint32_t* sync_host = nullptr;  // pinned, act_units + 2 words: d_err, twin[], twin_ok
+    // Fixed step: on a fixed point whose twin[] words the host knows to be 2,
+    // a step is life_still_step_kernel alone, launched directly.
+    // fixed_on: GOL_DEV_FIXED_STEP, 0 = off, 1 = on, 2 = after every step that ended with
+    // a remainder launch, seen or not (the error-status test); 0 wherever the plan or
+    // the switches leave one of the kernels the path stands for out (create).
+    // twin_two: gol_sync saw a 2 in every unit's word, and every step since ended with a
+    // remainder launch on the still field (twin_clear and a step that ends with a
+    // depth-K launch, which writes 1, withdraw it).  rem_ended: the engine's last step
+    // ended with a remainder launch, whatever happened since (fixed_on == 2 only).
+    // fixed_steps: steps that took the path; fixed_passes: their probe passes, each of
+    // which counts every one of plan 0's owned_tiles in kept[] and sure[] (added on the
+    // host, gol_activity_pass_kept / _sure, so that no step touches those arrays).
+    int fixed_on = 0;
+    bool twin_two = false;
+    bool rem_ended = false;
+    uint64_t fixed_steps = 0;
+    uint64_t fixed_passes = 0;
+    int64_t owned_tiles = 0;
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on

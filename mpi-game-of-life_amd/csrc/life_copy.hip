@@ -15,6 +15,8 @@ namespace gol {
 
 namespace {
 
+constexpr int kStillStepThreads = 1024;  // life_still_step_kernel's one workgroup
+
 // calm(U) as life_tb_kernel's prologue evaluates it: every streak_in of U's
 // neighbour list is >= 1, and an empty list is not calm (uniform); *still: every
 // one of them is >= 2, the condition on which a depth-K launch skips U.
@@ -97,6 +99,47 @@ __global__ __launch_bounds__(64) void life_still_span_kernel(uint32_t* busy, int
         *err = kErrShortStep;
 }
 
+// The fixed step (DESIGN §4 "Fixed step"): one workgroup, strided over the units, in
+// place of every kernel of a step that starts on a proven fixed point.  Phase 1 is the
+// proof itself, as gol_sync makes it on the host (engine.cpp sync_observing): twin_ok
+// set and a 2 in every unit's word.  Phase 2, behind the barrier that reduces phase 1,
+// adds the step's increments and stores its final values, none of which depends on what
+// a word held (engine.cpp still_effect derives them from the kernels).  Where the proof
+// fails one lane stores kErrShortStep and nothing else is written.  Plain vector loads
+// and stores by one workgroup: no atomics, no scratch, no field word touched.
+// Every index is below min(total_units, act_units), the length of every region.
+__global__ __launch_bounds__(kStillStepThreads) void life_still_step_kernel(StillArgs a)
+{
+    if (blockIdx.x != 0) return;
+    const uint32_t n = a.total_units;
+    int ok = n > 0 && n <= a.act_units && *a.twin_ok != 0u;
+    if (n <= a.act_units)
+        for (uint32_t u = threadIdx.x; u < n; u += kStillStepThreads) ok = ok && a.twin[u] == 2u;
+    if (!__syncthreads_and(ok)) {
+        if (threadIdx.x == 0) *a.err = kErrShortStep;
+        return;
+    }
+    for (uint32_t u = threadIdx.x; u < n; u += kStillStepThreads) {
+        a.act[2 * u] += a.computed;
+        a.act[2 * u + 1] += a.skipped;
+        a.copied[u] += a.n_copied;
+        a.probed[u] += a.n_probed;
+        a.pass_probed[u] += a.n_pass_probed;
+        a.elided[u] += a.n_elided;
+        a.streak0[u] = a.v_streak0;
+        a.streak1[u] = a.v_streak1;
+        a.need[u] = a.v_need;
+        a.held[u] = a.v_held;
+        a.moved[u] = a.v_moved;
+        a.twin[u] = a.v_twin;
+    }
+    if (threadIdx.x == 0) {
+        a.busy[0] += a.busy0_add;
+        a.busy[1] = a.busy1;
+        *a.twin_ok = a.v_twin_ok;
+    }
+}
+
 // One wavefront per tile of kCopyTileRows rows x kCopyTileWords words, lane l = word
 // l of the tile's column segment, consecutive tiles along a row chunk.  The tile is
 // copied when one of its owners has `need`, whole: the words of its other owners too.
@@ -174,6 +217,16 @@ hipError_t launch_still_span(uint32_t* busy, int* err, uint32_t first_idx, uint3
 {
     if (!busy || !err || count == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(life_still_span_kernel, dim3(1), dim3(64), 0, s, busy, err, first_idx, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_still_step(const StillArgs& a, hipStream_t s)
+{
+    if (!a.streak0 || !a.streak1 || !a.act || !a.copied || !a.busy || !a.probed || !a.need ||
+        !a.held || !a.elided || !a.moved || !a.pass_probed || !a.twin || !a.twin_ok || !a.err ||
+        a.total_units == 0 || a.total_units > a.act_units)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(life_still_step_kernel, dim3(1), dim3(kStillStepThreads), 0, s, a);
     return hipGetLastError();
 }
 

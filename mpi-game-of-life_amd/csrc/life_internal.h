@@ -298,6 +298,25 @@ constexpr int kErrShortStep = 2;
 hipError_t launch_still_span(uint32_t* busy, int* err, uint32_t first_idx, uint32_t count,
                              hipStream_t s);
 
+// The fixed step (DESIGN §4 "Fixed step"): one workgroup in place of every kernel of a
+// step on a proven fixed point.  The proof is *twin_ok != 0 and twin[u] == 2 for every
+// unit; where it holds the kernel adds the step's increments to the counters and
+// stores its final values to the state words (engine.cpp still_effect computes both),
+// else it stores kErrShortStep to *err and nothing else.  The regions are ActState's
+// (engine_internal.h), each of act_units words (act: 2 per unit), of which the first
+// total_units are touched.
+struct StillArgs {
+    uint32_t *streak0, *streak1, *act, *copied, *busy, *probed, *need, *held, *elided, *moved,
+        *pass_probed, *twin, *twin_ok;
+    int* err;
+    uint32_t total_units, act_units;
+    // increments per unit, and of busy[0]
+    uint32_t computed, skipped, n_copied, n_probed, n_pass_probed, n_elided, busy0_add;
+    // final values
+    uint32_t busy1, v_streak0, v_streak1, v_need, v_held, v_moved, v_twin, v_twin_ok;
+};
+hipError_t launch_still_step(const StillArgs& a, hipStream_t s);
+
 // The probe pass (life_probe.hip, DESIGN §4 "Probe pass"): one generation over the
 // copy pass's tiles before a step's first launch, in the copy pass's shape.  A device
 // table gives per tile the units one of whose rectangles, dilated by depth - 1

@@ -116,6 +116,7 @@ gol_status torus_create(uint64_t h, uint64_t w, const gol_config* cfg, gol_engin
     // (short step) the wrap withdraws the record before every round: the
     // inner engine's gol_sync has nothing to look for
     e->inner->short_on = 0;
+    e->inner->fixed_on = 0;  // (fixed step) stands on the short step
     if (e->inner->sync_host) {
         (void)hipHostFree(e->inner->sync_host);
         e->inner->sync_host = nullptr;

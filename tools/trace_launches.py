@@ -12,6 +12,9 @@ launch 3 (skips by its lists), launches 4-62 (the one-load exit; duration and pi
 the remainder likewise, and the step's span.  A short step (DESIGN §4 "Short step")
 has three depth-16 launches and life_still_span_kernel in place of the others: its
 duration is still_span_us, and launches_per_step counts every kernel of the step.
+A fixed step (DESIGN §4 "Fixed step") is life_still_step_kernel alone: a step of one
+kernel, whose duration is fixed_step_us and the step's span; fixed_steps counts them
+among the steps read.
 
     python tools/trace_launches.py TRACE_kernel_trace.csv [--steps 20] [--depth 16]
 """
@@ -38,7 +41,8 @@ def main():
         name = r["Kernel_Name"]
         kind = ("copy" if ("life_copy_kernel" in name or "life_calm_kernel" in name)
                 else "probe" if "life_probe_" in name
-                else "span" if "life_still_span_kernel" in name else depth_of(name))
+                else "span" if "life_still_span_kernel" in name
+                else "fixed" if "life_still_step_kernel" in name else depth_of(name))
         if kind is not None:
             ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), kind))
     ev.sort()
@@ -46,10 +50,14 @@ def main():
     steps, cur = [], []
     for s, e, kind in ev:
         cur.append((s, e, kind))
+        if kind == "fixed":  # a step of its own
+            steps.append(cur)
+            cur = []
+            continue
         if kind not in ("copy", "probe", "span") and kind != a.depth:
             steps.append(cur)
             cur = []
-    full = [st for st in steps if sum(1 for x in st if x[2] == a.depth) >= 4
+    full = [st for st in steps if st[-1][2] == "fixed" or sum(1 for x in st if x[2] == a.depth) >= 4
             or (any(x[2] == "span" for x in st) and sum(1 for x in st if x[2] == a.depth) == 3)][-a.steps:]
     cols = {}
 
@@ -57,6 +65,10 @@ def main():
         cols.setdefault(key, []).append(ns / 1e3)
 
     for st in full:
+        if st[-1][2] == "fixed":
+            add("fixed_step_us", st[-1][1] - st[-1][0])
+            add("step_span_us", st[-1][1] - st[0][0])
+            continue
         deep = [x for x in st if x[2] == a.depth]
         rem = st[-1]
         copies = [x for x in st if x[2] == "copy"]
@@ -84,7 +96,8 @@ def main():
             add("pass_remainder_us", pr[-1][1] - pr[0][0])
         add("remainder_with_pass_us", rem[1] - (pr[0][0] if pr else rem[0]))
         add("step_span_us", rem[1] - (pp[0][0] if pp else deep[0][0]))
-    out = {"steps": len(full), "launches_per_step": statistics.median(len(st) for st in full)}
+    out = {"steps": len(full), "fixed_steps": sum(1 for st in full if st[-1][2] == "fixed"),
+           "launches_per_step": statistics.median(len(st) for st in full)}
     out.update({k: round(statistics.median(v), 2) for k, v in cols.items()})
     print(json.dumps(out, indent=1))
 
