@@ -610,6 +610,56 @@ gol_status gol_batch_init_random(gol_batch* b, uint64_t seed);
 gol_status gol_batch_step(gol_batch* b, uint64_t generations);
 gol_status gol_batch_sync(gol_batch* b);
 
+/* Steps every field until it repeats with a period that divides `lag`, or for
+ * max_generations: gol_step_until_periodic for all n fields at once, in the batch
+ * kernel.  With F_i(g) field i's state g generations after the call, L = lag and
+ * C = check_every (0 means the least multiple of 64 that is >= L, as
+ * gol_step_until_periodic): checks happen at g = C, 2 C, ... <= max_generations, and the
+ * first such g with F_i(g) == F_i(g - L), cell for cell, ends field i's search:
+ * generation[i] = g and period[i] = the least divisor p of L with F_i(g - L + p) ==
+ * F_i(g - L), which is the cycle's minimal period (the orbit from g - L on is purely
+ * periodic, so its minimal period divides L).  No repeat found: period[i] = 0 and
+ * generation[i] = max_generations.  On return every field holds F_i(max_generations),
+ * word for word what gol_batch_step(b, max_generations) would have left: a field in a
+ * known cycle need not be computed to know that state, so a wavefront whose fields have
+ * all been found stops computing, and once every wavefront has, nothing more is
+ * launched.  The call is synchronous like gol_batch_digest; only n periods, n
+ * generations and a few counters cross to the host.  A later call counts from 0 again
+ * and forgets earlier results.  `period` and `generation` ([n] each) may be NULL.
+ * GOL_EINVAL, before anything is stepped: null batch or out, out->struct_size not
+ * sizeof(gol_batch_until), lag outside 1..1024 (no such lag has more than 32 divisors,
+ * which travel in the kernel's arguments), 0 < check_every < lag, check_every > 65536.
+ * max_generations == 0: GOL_OK with nothing run, every period and generation 0.
+ * The first call allocates a snapshot buffer as large as the batch (GOL_ENOMEM if that
+ * fails), freed by gol_batch_destroy. */
+typedef struct gol_batch_until {
+    uint32_t struct_size;      /* in: sizeof(gol_batch_until), as gol_until */
+    uint32_t lag, check_every; /* out: as used (check_every resolved from 0) */
+    uint32_t launches;         /* out: kernel launches issued by this call */
+    uint32_t reserved;
+    uint64_t found;            /* out: fields with period != 0 */
+    uint64_t wave_generations; /* out: generations computed, summed over wavefronts */
+} gol_batch_until;
+gol_status gol_batch_step_until_periodic(gol_batch* b, uint64_t max_generations, uint32_t lag,
+                                         uint32_t check_every, uint32_t* period,
+                                         uint64_t* generation, gol_batch_until* out);
+
+/* Host-only, no GPU: how gol_batch_step_until_periodic splits its work for a batch whose
+ * launch cap is launch_generations (the same GOL_EINVALs for lag and check_every; null
+ * out is GOL_EINVAL).  Every launch covers whole check intervals, each starting at a
+ * multiple of check_every; the last one also runs the tail. */
+typedef struct gol_batch_until_plan {
+    uint32_t check_every;        /* resolved */
+    uint32_t ndivisors;          /* proper divisors of lag, ascending, in divisors[] */
+    uint32_t divisors[32];
+    uint64_t checks;             /* max_generations / check_every */
+    uint32_t tail;               /* max_generations % check_every */
+    uint32_t checks_per_launch;  /* max(1, launch_generations / check_every) */
+    uint64_t launches;           /* ceil(checks / checks_per_launch), at least 1 if max_generations > 0 */
+} gol_batch_until_plan;
+gol_status gol_batch_until_plan_of(uint64_t max_generations, uint32_t lag, uint32_t check_every,
+                                   uint32_t launch_generations, gol_batch_until_plan* out);
+
 /* live[i], hash[i] = exactly what gol_digest returns for an h x w engine that holds
  * field first + i (either array may be NULL).  Only 2 * count words cross to the host. */
 gol_status gol_batch_digest(gol_batch* b, uint64_t first, uint64_t count, uint64_t* live,

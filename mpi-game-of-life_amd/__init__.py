@@ -49,7 +49,7 @@ EXPORTS = [
     "gol_batch_geometry", "gol_batch_create", "gol_batch_destroy", "gol_batch_info",
     "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
     "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step", "gol_batch_sync",
-    "gol_batch_digest",
+    "gol_batch_digest", "gol_batch_step_until_periodic", "gol_batch_until_plan_of",
 ]
 
 # gol_step_until_periodic flag: run on to max_generations once a period is known
@@ -139,6 +139,48 @@ class Until(ctypes.Structure):
 
     def __repr__(self):
         return "Until(" + ", ".join(f"{k}={getattr(self, k)}" for k, _ in self._fields_[1:]) + ")"
+
+
+class BatchUntil(ctypes.Structure):
+    """gol_batch_until: the counters of gol_batch_step_until_periodic."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),  # in: sizeof(gol_batch_until) (gol.h)
+        ("lag", ctypes.c_uint32),
+        ("check_every", ctypes.c_uint32),
+        ("launches", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("found", ctypes.c_uint64),
+        ("wave_generations", ctypes.c_uint64),
+    ]
+
+
+class BatchUntilPlan(ctypes.Structure):
+    """gol_batch_until_plan: how gol_batch_step_until_periodic splits its work."""
+    _fields_ = [
+        ("check_every", ctypes.c_uint32),
+        ("ndivisors", ctypes.c_uint32),
+        ("divisors", ctypes.c_uint32 * 32),
+        ("checks", ctypes.c_uint64),
+        ("tail", ctypes.c_uint32),
+        ("checks_per_launch", ctypes.c_uint32),
+        ("launches", ctypes.c_uint64),
+    ]
+
+
+class BatchPeriods:
+    """What BatchEngine.step_until_periodic found: period (uint32 [n], 0 = none) and
+    generation (uint64 [n]) per field, and the call's lag, check_every, launches, found
+    and wave_generations (gol_batch_until)."""
+
+    def __init__(self, period, generation, r):
+        self.period, self.generation = period, generation
+        self.lag, self.check_every, self.launches = r.lag, r.check_every, r.launches
+        self.found, self.wave_generations = r.found, r.wave_generations
+
+    def __repr__(self):
+        return (f"BatchPeriods(found={self.found}/{len(self.period)}, lag={self.lag}, "
+                f"check_every={self.check_every}, launches={self.launches}, "
+                f"wave_generations={self.wave_generations})")
 
 
 class SchedOp(ctypes.Structure):
@@ -276,10 +318,14 @@ def lib():
     L.gol_batch_step.argtypes = [vp, u64]
     L.gol_batch_sync.argtypes = [vp]
     L.gol_batch_digest.argtypes = [vp, u64, u64, vp, vp]
+    L.gol_batch_step_until_periodic.argtypes = [vp, u64, u32, u32, vp, vp,
+                                                ctypes.POINTER(BatchUntil)]
+    L.gol_batch_until_plan_of.argtypes = [u64, u32, u32, u32, ctypes.POINTER(BatchUntilPlan)]
     for name in ["gol_batch_geometry", "gol_batch_create", "gol_batch_info",
                  "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
                  "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step",
-                 "gol_batch_sync", "gol_batch_digest"]:
+                 "gol_batch_sync", "gol_batch_digest", "gol_batch_step_until_periodic",
+                 "gol_batch_until_plan_of"]:
         getattr(L, name).restype = ctypes.c_int
     for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit", "gol_snapshot",
                  "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
@@ -470,6 +516,19 @@ def batch_geometry(n, h, w, **cfg_kw):
                                     ctypes.byref(fpw), ctypes.byref(rows), ctypes.byref(waves)))
     return {"lanes_per_field": lpf.value, "fields_per_wave": fpw.value,
             "rows_in_regs": rows.value, "waves": waves.value}
+
+
+def batch_until_plan(max_generations, lag, check_every=0, launch_generations=4096):
+    """gol_batch_until_plan_of (host only, no GPU): how BatchEngine.step_until_periodic
+    splits its work on a batch whose launch cap is launch_generations.  Returns a dict:
+    check_every (resolved), divisors (lag's proper divisors, ascending), checks, tail,
+    checks_per_launch, launches."""
+    p = BatchUntilPlan()
+    _check(lib().gol_batch_until_plan_of(max_generations, lag, check_every, launch_generations,
+                                         ctypes.byref(p)))
+    return {"check_every": p.check_every, "divisors": list(p.divisors[:p.ndivisors]),
+            "checks": p.checks, "tail": p.tail, "checks_per_launch": p.checks_per_launch,
+            "launches": p.launches}
 
 
 def unique_id() -> bytes:
@@ -891,6 +950,21 @@ class BatchEngine:
 
     def sync(self):
         _check(lib().gol_batch_sync(self._h))
+
+    def step_until_periodic(self, max_generations, lag, check_every=0):
+        """Steps every field until it repeats with a period that divides `lag`, checking
+        every check_every generations (0: the least multiple of 64 >= lag), or for
+        max_generations (gol_batch_step_until_periodic).  On return every field holds
+        what step(max_generations) would have left.  Returns a BatchPeriods: period
+        (0 = none found) and generation per field, and the call's counters."""
+        import numpy as np
+        period = np.zeros(self.n, dtype=np.uint32)
+        generation = np.zeros(self.n, dtype=np.uint64)
+        r = BatchUntil(struct_size=ctypes.sizeof(BatchUntil))
+        _check(lib().gol_batch_step_until_periodic(self._h, max_generations, lag, check_every,
+                                                   period.ctypes.data, generation.ctypes.data,
+                                                   ctypes.byref(r)))
+        return BatchPeriods(period, generation, r)
 
     def digest(self, first=0, count=None):
         """(live, hash): two uint64 arrays [count], per field what Engine.digest()

@@ -3,11 +3,14 @@
 // life_batch_kernel launch per (at most) launch_generations generations (life_batch.h,
 // DESIGN §4 "life_batch_kernel").  Argument checks and the fixed geometry are host
 // code that never touches the GPU; the host forms of load and store are the device
-// forms behind a compact staging buffer.
+// forms behind a compact staging buffer.  gol_batch_step_until_periodic drives
+// life_batch_until_kernel (life_batch_until.h) launch by launch, by the host-only plan
+// of gol_batch_until_plan_of.
 #include <cstdlib>
 
 #include "engine_internal.h"
 #include "life_batch.h"
+#include "life_batch_until.h"
 
 struct gol_batch {
     int device = 0;
@@ -21,6 +24,12 @@ struct gol_batch {
     // staging for the host forms of load / store and for the digests, kept between calls
     uint64_t* stage = nullptr;
     size_t stage_words = 0;
+    // gol_batch_step_until_periodic, allocated by its first call: the snapshot buffer (as
+    // large as buf) and one block of [counters | generation[n] | period[n] | done[waves]];
+    // `counters`: where the block's counters start from and are read back to
+    uint64_t* snap = nullptr;
+    unsigned char* until = nullptr;
+    gol::BatchUntilCounters counters = {};
 };
 
 namespace golh __attribute__((visibility("hidden"))) {
@@ -134,6 +143,38 @@ gol_status stage_copy(gol_batch* b, uint64_t count, uint64_t* host, uint64_t fs,
     return GOL_OK;
 }
 
+gol::BatchArgs args_of(const gol_batch* b)
+{
+    gol::BatchArgs a{};
+    a.buf = b->buf;
+    a.waves = (int64_t)b->waves;
+    a.n = (int64_t)b->n;
+    a.h = (int32_t)b->h;
+    a.w = (int32_t)b->w;
+    a.wq = (int32_t)b->wq;
+    a.lpf_shift = (int32_t)b->lpf_shift;
+    a.torus = b->sem == GOL_SEM_TORUS;
+    a.birth = b->birth;
+    a.survive = b->survive;
+    a.lastmask = gol_split64(last_mask(b->w));
+    return a;
+}
+
+// The checks gol_batch_step_until_periodic and gol_batch_until_plan_of share;
+// *check_every: resolved from 0.
+gol_status until_args(uint32_t lag, uint32_t* check_every)
+{
+    if (lag < 1 || lag > gol::kBatchUntilMaxLag)
+        return fail(GOL_EINVAL, "a batch's lag must be 1..1024 (its proper divisors travel in "
+                                "the kernel's arguments)");
+    if (*check_every == 0)
+        *check_every = (lag + 63) / 64 * 64;
+    else if (*check_every < lag)
+        return fail(GOL_EINVAL, "check_every must be 0 or >= lag");
+    if (*check_every > 65536) return fail(GOL_EINVAL, "a batch's check_every must be <= 65536");
+    return GOL_OK;
+}
+
 }  // namespace
 
 }  // namespace golh
@@ -215,6 +256,8 @@ void gol_batch_destroy(gol_batch* b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->buf) (void)hipFree(b->buf);
     if (b->stage) (void)hipFree(b->stage);
+    if (b->snap) (void)hipFree(b->snap);
+    if (b->until) (void)hipFree(b->until);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -304,24 +347,121 @@ gol_status gol_batch_step(gol_batch* b, uint64_t generations)
     if (!b) return fail(GOL_EINVAL, "null batch");
     if (generations == 0) return GOL_OK;
     HIP_TRY(hipSetDevice(b->device));
-    gol::BatchArgs a{};
-    a.buf = b->buf;
-    a.waves = (int64_t)b->waves;
-    a.n = (int64_t)b->n;
-    a.h = (int32_t)b->h;
-    a.w = (int32_t)b->w;
-    a.wq = (int32_t)b->wq;
-    a.lpf_shift = (int32_t)b->lpf_shift;
-    a.torus = b->sem == GOL_SEM_TORUS;
-    a.birth = b->birth;
-    a.survive = b->survive;
-    a.lastmask = gol_split64(last_mask(b->w));
+    gol::BatchArgs a = args_of(b);
     for (uint64_t left = generations; left > 0;) {
         const uint64_t g = std::min<uint64_t>(left, b->launch_gens);
         a.gens = (int32_t)g;
         HIP_TRY(gol::launch_batch(a, (int)b->rows, b->rule, b->stream));
         left -= g;
     }
+    return GOL_OK;
+}
+
+gol_status gol_batch_until_plan_of(uint64_t max_generations, uint32_t lag, uint32_t check_every,
+                                   uint32_t launch_generations, gol_batch_until_plan* out)
+{
+    if (!out) return fail(GOL_EINVAL, "null out");
+    GOL_TRY(until_args(lag, &check_every));
+    gol_batch_until_plan p = {};
+    p.check_every = check_every;
+    for (uint32_t d = 1; d <= lag / 2; ++d)
+        if (lag % d == 0) p.divisors[p.ndivisors++] = d;  // (at most 31: lag <= 1024)
+    p.checks = max_generations / check_every;
+    p.tail = (uint32_t)(max_generations % check_every);
+    p.checks_per_launch = std::max<uint32_t>(1, launch_generations / check_every);
+    p.launches = (p.checks + p.checks_per_launch - 1) / p.checks_per_launch;
+    if (p.launches == 0 && max_generations > 0) p.launches = 1;
+    *out = p;
+    return GOL_OK;
+}
+
+gol_status gol_batch_step_until_periodic(gol_batch* b, uint64_t max_generations, uint32_t lag,
+                                         uint32_t check_every, uint32_t* period,
+                                         uint64_t* generation, gol_batch_until* out)
+{
+    if (!out) return fail(GOL_EINVAL, "null out");
+    if (out->struct_size != sizeof(gol_batch_until))
+        return fail(GOL_EINVAL, "gol_batch_until.struct_size must be sizeof(gol_batch_until)");
+    GOL_TRY(until_args(lag, &check_every));
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    gol_batch_until_plan plan;
+    GOL_TRY(gol_batch_until_plan_of(max_generations, lag, check_every, b->launch_gens, &plan));
+    gol_batch_until r = {};
+    r.struct_size = sizeof(gol_batch_until);
+    r.lag = lag;
+    r.check_every = check_every;
+    if (max_generations == 0) {
+        for (uint64_t i = 0; i < b->n; ++i) {
+            if (period) period[i] = 0;
+            if (generation) generation[i] = 0;
+        }
+        *out = r;
+        return GOL_OK;
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t gen_off = sizeof(gol::BatchUntilCounters), per_off = gen_off + b->n * 8,
+                 done_off = per_off + b->n * 4, block = done_off + b->waves * 4;
+    if (!b->snap) {
+        if (hipMalloc(&b->snap, (size_t)b->waves * b->h * 64 * sizeof(uint64_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            b->snap = nullptr;
+            return fail(GOL_ENOMEM, "the batch's snapshot buffer");
+        }
+    }
+    if (!b->until) {
+        if (hipMalloc(&b->until, block) != hipSuccess) {
+            (void)hipGetLastError();
+            b->until = nullptr;
+            return fail(GOL_ENOMEM, "the batch's period results");
+        }
+    }
+    // results, done words and counters start from 0, the pending waves from all of them
+    HIP_TRY(hipMemsetAsync(b->until, 0, block, b->stream));
+    b->counters = gol::BatchUntilCounters{0ull, (uint32_t)b->waves, 0u};
+    // (b->counters is next written by the copy back after the first launch, on this stream)
+    HIP_TRY(hipMemcpyAsync(b->until, &b->counters, sizeof(b->counters), hipMemcpyHostToDevice,
+                           b->stream));
+    gol::BatchUntilArgs u{};
+    u.a = args_of(b);
+    u.snap = b->snap;
+    u.ctr = reinterpret_cast<gol::BatchUntilCounters*>(b->until);
+    u.generation = reinterpret_cast<uint64_t*>(b->until + gen_off);
+    u.period = reinterpret_cast<uint32_t*>(b->until + per_off);
+    u.done = reinterpret_cast<uint32_t*>(b->until + done_off);
+    u.max_g = max_generations;
+    u.lag = lag;
+    u.check_every = check_every;
+    u.ndiv = plan.ndivisors;
+    for (uint32_t k = 0; k < plan.ndivisors; ++k) u.div[k] = plan.divisors[k];
+    for (uint64_t j = 0; j < plan.launches; ++j) {
+        const uint64_t c0 = j * plan.checks_per_launch;
+        u.g0 = c0 * check_every;
+        u.intervals = (uint32_t)std::min<uint64_t>(plan.checks_per_launch, plan.checks - c0);
+        u.tail = j + 1 == plan.launches ? plan.tail : 0;
+        HIP_TRY(gol::launch_batch_until(u, (int)b->rows, b->rule, b->stream));
+        r.launches += 1;
+        // a few bytes per launch: once no wavefront is pending, every field already holds
+        // generation max_generations and nothing more is launched
+        HIP_TRY(hipMemcpyAsync(&b->counters, b->until, sizeof(b->counters), hipMemcpyDeviceToHost,
+                               b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        if (b->counters.pending == 0) break;
+    }
+    r.wave_generations = b->counters.wave_generations;
+    std::vector<uint32_t> per(b->n);
+    std::vector<uint64_t> gen(generation ? b->n : 0);
+    HIP_TRY(hipMemcpyAsync(per.data(), b->until + per_off, b->n * 4, hipMemcpyDeviceToHost,
+                           b->stream));
+    if (generation)
+        HIP_TRY(hipMemcpyAsync(gen.data(), b->until + gen_off, b->n * 8, hipMemcpyDeviceToHost,
+                               b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (uint64_t i = 0; i < b->n; ++i) {
+        if (per[i]) r.found += 1;
+        if (period) period[i] = per[i];
+        if (generation) generation[i] = per[i] ? gen[i] : max_generations;
+    }
+    *out = r;
     return GOL_OK;
 }
 

@@ -242,6 +242,8 @@ __device__ __forceinline__ void batch_pass(Pl<2> (&x)[R], Pl<2>& last, int32_t h
     }
 }
 
+// (life_batch_until.h's batch_until_run repeats the lane setup and the row load below
+// line for line, so that this kernel compiles as it did: change both together)
 template <int R, int RULE, bool TORUS, bool MULTI>
 __device__ __forceinline__ void batch_run(const BatchArgs& a, int64_t wave, int lane)
 {

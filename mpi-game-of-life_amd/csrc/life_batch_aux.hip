@@ -1,4 +1,4 @@
-// life_batch_aux.hip -- the batch kernel's dispatch over rows_in_regs and the
+// life_batch_aux.hip -- the batch kernels' dispatch over rows_in_regs and the
 // memory-bound codec kernels between the batch buffer's internal order and the
 // canonical [n][h][words] order (load, store, random init, digest); see life_batch.h.
 #include <hip/hip_runtime.h>
@@ -6,6 +6,7 @@
 
 #include "bitlayout.h"
 #include "life_batch.h"
+#include "life_batch_until.h"
 
 namespace gol {
 
@@ -21,6 +22,22 @@ hipError_t launch_batch(const BatchArgs& a, int rows, RuleKind rule, hipStream_t
     case 16: return launch_batch_rows<16>(a, rule, s);
     case 32: return launch_batch_rows<32>(a, rule, s);
     case 64: return launch_batch_rows<64>(a, rule, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern template hipError_t launch_batch_until_rows<8>(const BatchUntilArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_until_rows<16>(const BatchUntilArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_until_rows<32>(const BatchUntilArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_until_rows<64>(const BatchUntilArgs&, RuleKind, hipStream_t);
+
+hipError_t launch_batch_until(const BatchUntilArgs& u, int rows, RuleKind rule, hipStream_t s)
+{
+    switch (rows) {
+    case 8: return launch_batch_until_rows<8>(u, rule, s);
+    case 16: return launch_batch_until_rows<16>(u, rule, s);
+    case 32: return launch_batch_until_rows<32>(u, rule, s);
+    case 64: return launch_batch_until_rows<64>(u, rule, s);
     default: return hipErrorInvalidValue;
     }
 }
