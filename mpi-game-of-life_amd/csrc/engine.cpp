@@ -1,7 +1,7 @@
 // engine.cpp -- host side of libgol.so: the C ABI of include/gol.h.  This unit:
-// engine lifecycle, load/store, single-field and resident steps, launches and
-// timing, digests and plan queries; planning is plan.cpp, multi-GPU stripes
-// stripes.cpp, torus engines torus.cpp (engine_internal.h).
+// engine lifecycle, load/store, the resident step, launches and timing, digests
+// and plan queries; planning is plan.cpp, the single-stream step step.cpp, multi-GPU
+// stripes stripes.cpp, torus engines torus.cpp (engine_internal.h).
 //
 // Owns device memory, the HIP streams, the halo transport (RCCL communicator,
 // a caller's host transport, or device copies inside a group) and the launch
@@ -355,16 +355,8 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
             // anything else keeps the short graph.
             const char* fx = std::getenv("GOL_DEV_FIXED_STEP");
             const int fv = fx ? std::atoi(fx) : 1;
-            bool whole = e->short_on != 0 && e->through_on >= 2 && e->elide_on && e->sure_on &&
-                         e->nbuf == 2 && !e->xcd_shift && e->nranks <= 1 && p0.segs.size() == 1 &&
-                         p0.npass == 1 && p0.d_nb && p0.total_units > 0 &&
-                         p0.total_units <= e->act_units && p0.total_units <= 0xFFFFFFFFll;
-            // no launch of the step runs hand-off row blocks (launch(): such a launch
-            // leaves the activity state alone)
-            for (int d : gol::kDepthList)
-                if ((uint32_t)d <= e->K && p0.hand && p0.multi_blk && e->side[0] &&
-                    handoff_fits(p0.rpw, d, e->planes) && gol::handoff_kernel_exists(d, e->rule))
-                    whole = false;
+            bool whole = e->short_on != 0 && every_kernel_on(step_traits(e)) &&
+                         p0.total_units > 0 && p0.total_units <= 0xFFFFFFFFll;
             if (whole) {
                 // every unit owns rows (life_stencil.h: a unit without rows neither
                 // probes nor writes held = 1) ...
@@ -640,18 +632,66 @@ gol_status step_resident(gol_engine* e, uint64_t generations)
     return GOL_OK;
 }
 
-// `passes` > 1: a multi-pass launch of that many depth-K passes (plans with npass
-// >= passes), reading buf[cur] and writing buf[cur + 1 .. cur + passes]
-
-gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_t stream,
-                  int passes)
+// A launch of plan `p` at `depth` on the stream of `region` runs hand-off row blocks.
+static bool launch_hands(const gol_engine* e, const gol_engine::Plan& p, int region, uint32_t depth)
 {
-    hipStream_t s = stream ? stream : e->stream;
-    const int region = (e->band_stream && s == e->band_stream) ? 1 : 0;
-    const auto& p = e->plans[plan];
-    if (passes < 1 || (passes > 1 && (passes > p.npass || depth != e->K || !e->mpflags)))
-        return fail(GOL_ESTATE, "multi-pass launch of a plan without passes");
-    StepArgs a{};
+    return p.hand && p.multi_blk && e->side[region] && handoff_fits(p.rpw, (int)depth, e->planes) &&
+           gol::handoff_kernel_exists((int)depth, e->rule);
+}
+
+// (r06 dev A/B, GOL_DEV_XCD_SHIFT) per-XCD row shift between paired blocks: blocks
+// keep >= the length their closure needs after giving up 8 rows
+static bool launch_shifts(const gol_engine* e, const gol_engine::Plan& p, bool hand, uint32_t depth)
+{
+    if (!e->xcd_shift || p.segs.size() != 1) return false;
+    const int64_t shortest = p.rows_old ? std::min<int64_t>(p.rows_old, p.rows_young) : p.rpw;
+    return hand ? handoff_fits(shortest - 8, (int)depth, e->planes) : shortest - 8 >= 2;
+}
+
+// What the step's schedule (step_plan.h) reads of the engine and of plan 0.
+const StepTraits& step_traits(gol_engine* e)
+{
+    if (e->traits_ok) return e->traits;
+    StepTraits t;
+    t.K = e->K;
+    t.nbuf = e->nbuf;
+    t.tracked = e->d_streak && e->nranks <= 1;
+    t.has_err = e->d_err != nullptr;
+    t.act_on = e->act_on;
+    t.through_on = e->through_on;
+    t.pass_on = e->pass_on;
+    t.still_on = e->still_on;
+    t.probe_on = e->probe_on;
+    t.elide_on = e->elide_on;
+    t.ppass_on = e->ppass_on;
+    t.twin_on = e->twin_on;
+    t.sure_on = e->sure_on;
+    t.timing_every = e->timing_every;
+    t.planes2 = e->planes == 2;
+    static_assert(std::size(gol::kDepthList) <= (size_t)StepTraits::kMaxDepths, "depth list");
+    for (int d : gol::kDepthList) t.depth[t.ndepth++] = d;
+    if (!e->plans.empty()) {
+        const auto& p = e->plans[0];
+        t.npass = p.npass;
+        t.has_nb = p.d_nb != nullptr;
+        t.has_own = p.d_own != nullptr;
+        t.has_ptab = p.d_ptab != nullptr;
+        t.one_seg = p.segs.size() == 1;
+        t.units_fit = p.total_units <= e->act_units;
+        for (int i = 0; i < t.ndepth; ++i) {
+            t.hand[i] = launch_hands(e, p, 0, (uint32_t)t.depth[i]);
+            t.shift[i] = launch_shifts(e, p, t.hand[i], (uint32_t)t.depth[i]);
+        }
+    }
+    e->traits = t;
+    e->traits_ok = true;
+    return e->traits;
+}
+
+// The arguments every stencil launch takes, whoever issues it.
+static gol_status fill_step_args(const gol_engine* e, const gol_engine::Plan& p, uint32_t depth,
+                                 int passes, int region, bool hand, StepArgs& a)
+{
     for (int i = 0; i <= passes; ++i) a.pbuf[i] = e->buf[(e->cur + i) % e->nbuf];
     a.npass = passes;
     a.shadow_off = e->shadow_off;
@@ -673,9 +713,6 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     a.total_units = p.total_units;
     a.birth = e->birth;
     a.survive = e->survive;
-    const bool hand = p.hand && p.multi_blk && e->side[region] &&
-                      handoff_fits(p.rpw, (int)depth, e->planes) &&
-                      gol::handoff_kernel_exists((int)depth, e->rule);
     if (hand) {
         a.side = e->side[region];
         a.flags = e->flags[region];
@@ -692,13 +729,7 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
         a.rows_old = p.rows_old;
         a.units_old = p.units_old;
     }
-    // (r06 dev A/B, GOL_DEV_XCD_SHIFT) per-XCD row shift between paired blocks:
-    // blocks keep >= the length their closure needs after giving up 8 rows
-    if (e->xcd_shift && p.segs.size() == 1) {
-        const int64_t shortest = p.rows_old ? std::min<int64_t>(p.rows_old, p.rows_young) : p.rpw;
-        const bool fits = hand ? handoff_fits(shortest - 8, (int)depth, e->planes) : shortest - 8 >= 2;
-        if (fits) a.xcd_shift = e->xcd_shift;
-    }
+    if (launch_shifts(e, p, hand, depth)) a.xcd_shift = e->xcd_shift;
     a.edge = p.edge;
     a.right_q0 = p.right_q0;
     a.half_q0 = p.half_q0;
@@ -706,226 +737,218 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     a.pair_units = p.pair_units;
     a.pair0 = p.total_units - p.pair_units;
     a.pairs = p.dpairs;
-    // activity skip: launches of a gol_step of a single-stream engine (step_single
-    // counts them in act_launch; the autotuner's and every other launch: -1).  The
-    // streaks live within one step: its first launch carries no history, the
-    // parity alternates from there, and a launch at another depth (the remainder,
-    // always last) never skips and leaves the streaks alone: it reads the ones the
-    // last depth-K launch wrote, and only to copy still units through (its depths
-    // add up to less than K, so the lists, dilated by K, cover every one of them).
-    bool pass = false;  // the copy pass goes before this launch
-    // copy elision: the pass may take ActState::held (case P) / every calm unit's
-    // rows are in the output buffer already (case R)
-    bool pass_held = false, pass_all = false;
-    // Rows both buffers hold (DESIGN §4): a launch of plan 0 writes the field, so it
-    // clears twin_ok unless it is a launch of an activity step, whose last launch
-    // decides: twin_last = that launch, reading history, so that the calm kernel can
-    // write twin[] before it; if none does, the flag goes.
-    bool twin_drop = e->twin_on && e->d_streak && plan == 0;
-    bool twin_last = false, twin_set = false;
-    // Sure tiles: the value the calm kernel writes for a calm unit.  2 only
-    // in the remainder branch below, where fewer than K generations have run since the
-    // streaks were written; a depth-K launch and the held writer keep 1.
-    uint32_t twin_val = 1;
-    bool short_ok = false;
-    if (e->act_launch >= 0 && e->d_streak && plan == 0 && e->nranks <= 1) {
-        const ActState st{e->d_streak, (size_t)e->act_units};
-        a.act = st.act();
-        a.copied = st.copied();
-        const bool may = e->act_on && !e->timing_every && !hand && passes == 1 && p.d_nb &&
-                         p.npass == 1 && e->nbuf == 2 && !a.xcd_shift &&
-                         p.total_units <= e->act_units;
-        if (may && depth == e->K) {
-            const int par = e->act_launch & 1;
-            a.streak_in = st.streak(par);
-            a.streak_out = st.streak(par ^ 1);
-            a.nb_off = p.d_nb;
-            a.nb_ids = p.d_nb + p.nb_off.size();
-            a.no_hist = e->act_launch == 0 ? 1 : 0;
-            a.probe = (a.no_hist && e->probe_on) ? 1 : 0;
-            a.probed = st.probed();
-            // (copy elision) a first launch that probes writes every unit's flag
-            a.held = (a.probe && e->elide_on) ? st.held() : nullptr;
-            if (a.no_hist) e->act_probed = a.held != nullptr;
-            a.through = e->through_on >= 1 ? 1 : 0;
-            a.busy = e->still_on ? st.busy() : nullptr;
-            a.launch_idx = e->act_launch;
-            e->act_hist = par ^ 1;
-            // the step's second launch: its streaks are 0 or 1, no unit can skip
-            pass = a.through && e->act_launch == 1;
-            pass_held = e->act_probed;
-            twin_drop = e->twin_on && e->act_last;
-            twin_last = twin_drop && !a.no_hist;
-            // a launch the short step leaves out would have taken the one-load exit
-            short_ok = a.busy && !a.no_hist && a.launch_idx >= 3;
-        } else if (may && depth < e->K && e->act_hist >= 0 && e->through_on >= 2) {
-            a.streak_in = st.streak(e->act_hist);
-            a.nb_off = p.d_nb;
-            a.nb_ids = p.d_nb + p.nb_off.size();
-            a.through = 1;
-            pass = true;  // a remainder launch never skips
-            // the step's second launch: the first one's input is this one's output
-            pass_held = e->act_probed && e->act_launch == 1;
-            // a later launch of the same remainder: the same streaks, the buffers
-            // swapped, and every calm unit's rows went across (or were there) in the
-            // launch before
-            pass_all = e->act_rem > 0;
-            ++e->act_rem;
-            twin_last = twin_drop = e->twin_on && e->act_last;
-            if (e->sure_on) twin_val = 2;
-        } else {
-            e->act_hist = -1;
-            e->act_probed = false;
-        }
-        ++e->act_launch;
-    }
-    // Copy pass (life_copy.hip): the calm units' rows, stored by a kernel
-    // of its own on this stream (captured into the step's graph with the launch);
-    // the launch's calm units then store no row (through = 2).  Both read the same
-    // streaks, which neither writes before the launch's units have read them.
-    if (pass && e->pass_on && p.d_own && s == e->stream && p.segs.size() == 1) {
-        // The pass writes whole tiles, words of units that are not calm among them.
-        // That is safe only where every such unit stores its whole rectangle in
-        // the launch that follows: no unit of it may skip.  A remainder launch
-        // writes no streaks and never skips; a depth-K launch skips on streaks >= 2,
-        // which the step's second launch cannot see (the first wrote 0 or 1).
-        const bool none_skips = !a.streak_out || (a.launch_idx == 1 && !a.no_hist);
-        if (!none_skips || !a.streak_in || a.through != 1)
-            return fail(GOL_ESTATE, "copy pass before a launch whose units may skip");
-        const SegDesc& sg = p.segs[0];
-        gol::CopyArgs c{};
-        c.src = a.pbuf[0];
-        c.dst = a.pbuf[1];
-        c.owners = p.d_own;
-        const ActState st{e->d_streak, (size_t)e->act_units};
-        c.need = st.need();
-        // copy elision (GOL_DEV_COPY_ELIDE=0: elided null, every calm unit copies)
-        c.elided = e->elide_on ? st.elided() : nullptr;
-        c.held = (e->elide_on && pass_held) ? st.held() : nullptr;
-        c.all_held = (e->elide_on && pass_all) ? 1 : 0;
-        c.streak_in = a.streak_in;
-        c.nb_off = a.nb_off;
-        c.nb_ids = a.nb_ids;
-        c.stride = a.stride;
-        c.base_row = sg.base_row;
-        c.lastmask = e->lastmask_split[0];
-        c.ntile = (int32_t)(p.owners.size() / gol::kCopyOwners);
-        c.ncol = p.copy_ncol;
-        c.total_units = (int32_t)p.total_units;
-        c.out_lo = (int32_t)sg.out_lo;
-        c.out_hi = (int32_t)sg.out_hi;
-        c.ng = (int32_t)e->ng;
-        c.vlo = (int32_t)std::max<int64_t>(0, -sg.glob0);
-        c.vhi = (int32_t)std::max<int64_t>(0, std::min(sg.in_rows, sg.field_h - sg.glob0));
-        // the step's last launch: the calm kernel writes twin[] as well
-        if (twin_last) {
-            c.twin = st.twin();
-            c.twin_ok = st.twin_ok();
-            c.twin_val = twin_val;
-            twin_set = true;
-        }
-        HIP_TRY(gol::launch_copy_pass(c, s));
-        a.through = 2;
-    }
-    // ... and where that launch takes no copy pass (a depth-K launch after the step's
-    // second), the calm kernel runs for twin[] alone, on the streaks the launch reads
-    if (twin_last && !twin_set && a.streak_in && a.nb_off && !a.no_hist) {
-        const ActState st{e->d_streak, (size_t)e->act_units};
-        gol::CopyArgs c{};
-        c.streak_in = a.streak_in;
-        c.nb_off = a.nb_off;
-        c.nb_ids = a.nb_ids;
-        c.total_units = (int32_t)p.total_units;
-        c.twin = st.twin();
-        c.twin_ok = st.twin_ok();
-        HIP_TRY(gol::launch_twin_flags(c, s));
-        twin_set = true;
-    }
-    // Probe pass (life_probe.hip): before a step's first launch, where that
-    // launch probes, under the copy pass's conditions.  The launch has no history, so
-    // none of its units skips or copies: a unit the pass leaves unmarked ends quiet on
-    // the pass's word, every other one stores its whole rectangle after the pass.
-    if (a.probe && e->ppass_on && p.d_ptab && s == e->stream && p.segs.size() == 1 &&
-        e->planes == 2) {
-        if (!a.no_hist || !a.streak_out)
-            return fail(GOL_ESTATE, "probe pass before a launch with history");
-        const SegDesc& sg = p.segs[0];
-        const ActState st{e->d_streak, (size_t)e->act_units};
-        gol::ProbeArgs c{};
-        c.src = a.pbuf[0];
-        c.dst = a.pbuf[1];
-        c.tiles = p.d_ptab;
-        c.moved = st.moved();
-        c.stride = a.stride;
-        c.base_row = sg.base_row;
-        c.lastmask = e->lastmask_split[0];
-        c.ntile = (int32_t)(p.probe_tiles.size() / gol::kProbeSlots);
-        c.ncol = p.copy_ncol;
-        c.total_units = (int32_t)p.total_units;
-        c.out_lo = (int32_t)sg.out_lo;
-        c.out_hi = (int32_t)sg.out_hi;
-        c.ng = (int32_t)e->ng;
-        c.vlo = (int32_t)std::max<int64_t>(0, -sg.glob0);
-        c.vhi = (int32_t)std::max<int64_t>(0, std::min(sg.in_rows, sg.field_h - sg.glob0));
-        c.birth = e->birth;
-        c.survive = e->survive;
-        // rows both buffers hold: the copy pass's owners, over the same tile grid
-        if (e->twin_on && p.d_own && e->d_kept) {
-            if (p.owners.size() / gol::kCopyOwners != (size_t)c.ntile ||
-                e->kept_tiles != (int64_t)c.ntile || p.copy_ncol != c.ncol)
-                return fail(GOL_ESTATE, "probe pass and copy pass over different tiles");
-            c.owners = p.d_own;
-            c.twin = st.twin();
-            c.twin_ok = st.twin_ok();
-            c.kept = e->d_kept;
-            c.sure = e->sure_on ? e->d_sure : nullptr;
-        }
-        HIP_TRY(gol::launch_probe_pass(c, e->rule, s));
-        a.moved = st.moved();
-        a.pass_probed = st.pass_probed();
-    }
-    // the step's only launch, which probes and writes held[] for every unit: twin[] is
-    // held[], copied behind the launch
-    const bool twin_held = twin_drop && !twin_set && a.no_hist && a.probe && a.held;
-    // after the probe pass, which reads the flag as the step before left it
-    if (twin_drop && !twin_set && !twin_held) GOL_TRY(twin_clear(e, s));
 #if GOL_WAVE_LOG
     a.wlog = g_dev_wave_log;
 #endif
+    return GOL_OK;
+}
+
+// ... and what a launch of a single-stream step does with the activity state, as its
+// record says.
+static void fill_activity_args(const gol_engine* e, const gol_engine::Plan& p, const StepLaunch& r,
+                               StepArgs& a)
+{
+    if (!r.act) return;
+    const ActState st{e->d_streak, (size_t)e->act_units};
+    a.act = st.act();
+    a.copied = st.copied();
+    if (r.streak_in < 0) return;
+    a.streak_in = st.streak(r.streak_in);
+    a.nb_off = p.d_nb;
+    a.nb_ids = p.d_nb + p.nb_off.size();
+    if (r.streak_out) {
+        a.streak_out = st.streak(r.streak_in ^ 1);
+        a.probed = st.probed();
+    }
+    a.no_hist = r.no_hist ? 1 : 0;
+    a.probe = r.probe ? 1 : 0;
+    a.held = r.held ? st.held() : nullptr;
+    a.through = r.through;
+    a.busy = r.busy ? st.busy() : nullptr;
+    a.launch_idx = r.launch_idx;
+}
+
+// The tile grid of plan p's one segment, which the copy pass and the probe pass share.
+template <class Args>
+static void fill_tile_args(const gol_engine* e, const gol_engine::Plan& p, const StepArgs& a,
+                           size_t ntile, Args& c)
+{
+    const SegDesc& sg = p.segs[0];
+    c.src = a.pbuf[0];
+    c.dst = a.pbuf[1];
+    c.stride = a.stride;
+    c.base_row = sg.base_row;
+    c.lastmask = e->lastmask_split[0];
+    c.ntile = (int32_t)ntile;
+    c.ncol = p.copy_ncol;
+    c.total_units = (int32_t)p.total_units;
+    c.out_lo = (int32_t)sg.out_lo;
+    c.out_hi = (int32_t)sg.out_hi;
+    c.ng = (int32_t)e->ng;
+    c.vlo = (int32_t)std::max<int64_t>(0, -sg.glob0);
+    c.vhi = (int32_t)std::max<int64_t>(0, std::min(sg.in_rows, sg.field_h - sg.glob0));
+}
+
+// Copy pass (life_copy.hip): the calm units' rows, stored by a kernel of its
+// own on this stream (captured into the step's graph with the launch); the launch's
+// calm units then store no row (through = 2).  Both read the same streaks, which
+// neither writes before the launch's units have read them.
+static gol_status issue_copy_pass(gol_engine* e, const gol_engine::Plan& p, const StepLaunch& r,
+                                  const StepArgs& a, hipStream_t s)
+{
+    // The pass writes whole tiles, words of units that are not calm among them.
+    // That is safe only where every such unit stores its whole rectangle in
+    // the launch that follows: no unit of it may skip.  A remainder launch
+    // writes no streaks and never skips; a depth-K launch skips on streaks >= 2,
+    // which the step's second launch cannot see (the first wrote 0 or 1).
+    const bool none_skips = !a.streak_out || (a.launch_idx == 1 && !a.no_hist);
+    if (!none_skips || !a.streak_in || a.through != 2 || !p.d_own || s != e->stream ||
+        p.segs.size() != 1)
+        return fail(GOL_ESTATE, "copy pass before a launch whose units may skip");
+    const ActState st{e->d_streak, (size_t)e->act_units};
+    gol::CopyArgs c{};
+    fill_tile_args(e, p, a, p.owners.size() / gol::kCopyOwners, c);
+    c.owners = p.d_own;
+    c.need = st.need();
+    // copy elision (GOL_DEV_COPY_ELIDE=0: elided null, every calm unit copies)
+    c.elided = r.pass_elide ? st.elided() : nullptr;
+    c.held = r.pass_held ? st.held() : nullptr;
+    c.all_held = r.pass_all ? 1 : 0;
+    c.streak_in = a.streak_in;
+    c.nb_off = a.nb_off;
+    c.nb_ids = a.nb_ids;
+    // the step's last launch: the calm kernel writes twin[] as well
+    if (r.twin == StepLaunch::kTwinCalm) {
+        c.twin = st.twin();
+        c.twin_ok = st.twin_ok();
+        c.twin_val = r.twin_val;
+    }
+    HIP_TRY(gol::launch_copy_pass(c, s));
+    return GOL_OK;
+}
+
+// ... and where the step's last launch takes no copy pass (a depth-K launch after the
+// step's second), the calm kernel runs for twin[] alone, on the streaks the launch reads
+static gol_status issue_calm_alone(gol_engine* e, const gol_engine::Plan& p, const StepArgs& a,
+                                   hipStream_t s)
+{
+    const ActState st{e->d_streak, (size_t)e->act_units};
+    gol::CopyArgs c{};
+    c.streak_in = a.streak_in;
+    c.nb_off = a.nb_off;
+    c.nb_ids = a.nb_ids;
+    c.total_units = (int32_t)p.total_units;
+    c.twin = st.twin();
+    c.twin_ok = st.twin_ok();
+    HIP_TRY(gol::launch_twin_flags(c, s));
+    return GOL_OK;
+}
+
+// Probe pass (life_probe.hip): before a step's first launch, where that
+// launch probes, under the copy pass's conditions.  The launch has no history, so
+// none of its units skips or copies: a unit the pass leaves unmarked ends quiet on
+// the pass's word, every other one stores its whole rectangle after the pass.
+static gol_status issue_probe_pass(gol_engine* e, const gol_engine::Plan& p, const StepLaunch& r,
+                                   StepArgs& a, hipStream_t s)
+{
+    if (!a.no_hist || !a.streak_out || !a.probe || !p.d_ptab || s != e->stream ||
+        p.segs.size() != 1 || e->planes != 2)
+        return fail(GOL_ESTATE, "probe pass before a launch with history");
+    const ActState st{e->d_streak, (size_t)e->act_units};
+    gol::ProbeArgs c{};
+    fill_tile_args(e, p, a, p.probe_tiles.size() / gol::kProbeSlots, c);
+    c.tiles = p.d_ptab;
+    c.moved = st.moved();
+    c.birth = e->birth;
+    c.survive = e->survive;
+    // rows both buffers hold: the copy pass's owners, over the same tile grid
+    if (r.probe_twin) {
+        if (!p.d_own || !e->d_kept || p.owners.size() / gol::kCopyOwners != (size_t)c.ntile ||
+            e->kept_tiles != (int64_t)c.ntile || p.copy_ncol != c.ncol)
+            return fail(GOL_ESTATE, "probe pass and copy pass over different tiles");
+        c.owners = p.d_own;
+        c.twin = st.twin();
+        c.twin_ok = st.twin_ok();
+        c.kept = e->d_kept;
+        c.sure = r.probe_sure ? e->d_sure : nullptr;
+    }
+    HIP_TRY(gol::launch_probe_pass(c, e->rule, s));
+    a.moved = st.moved();
+    a.pass_probed = st.pass_probed();
+    return GOL_OK;
+}
+
+// The end of the timing bracket around a stencil launch, with the launch's work.
+static gol_status timing_end_launch(gol_engine* e, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
+                                    const gol_engine::Plan& p, uint32_t depth, int passes, bool hand)
+{
+    // cell-generations the lanes actually process: every stage of a block
+    // computes its rows, a classic block (and the last block of a hand-off
+    // segment) also d(d-1) stage-rows of vertical halo, and every strip also
+    // its 2 halo lanes
+    double comp = 0;
+    for (const auto& sg : p.segs) {
+        const double n = (double)std::max<int64_t>(0, sg.out_hi - sg.out_lo);
+        const double classic = hand ? (double)std::min<int64_t>(1, sg.nblk) : (double)sg.nblk;
+        comp += depth * n + classic * depth * (depth - 1.0);
+    }
+    // (the half strip's units: 64 lanes over one block's rows each, classic)
+    double comp_half = 0;
+    for (size_t i = 0; i + 2 < p.pairs.size(); i += 3)
+        comp_half += depth * (double)p.pairs[i + 2] + depth * (depth - 1.0);
+    const double cols = 64.0 * 32.0 * e->planes;  // per strip or unit
+    double rows = 0;
+    for (const auto& sg : p.segs) rows += (double)std::max<int64_t>(0, sg.out_hi - sg.out_lo);
+    return timing_end(e, s, e0, e1, p.own_rows * (double)e->W * depth * passes,
+                      (comp * p.groups + comp_half) * cols * passes, rows * passes);
+}
+
+// `passes` > 1: a multi-pass launch of that many depth-K passes (plans with npass
+// >= passes), reading buf[cur] and writing buf[cur + 1 .. cur + passes]
+
+gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_t stream,
+                  int passes, const StepLaunch* rec, bool skip_stencil)
+{
+    hipStream_t s = stream ? stream : e->stream;
+    const int region = (e->band_stream && s == e->band_stream) ? 1 : 0;
+    const auto& p = e->plans[plan];
+    if (passes < 1 || (passes > 1 && (passes > p.npass || depth != e->K || !e->mpflags)))
+        return fail(GOL_ESTATE, "multi-pass launch of a plan without passes");
+    const bool hand = launch_hands(e, p, region, depth);
+    StepArgs a{};
+    GOL_TRY(fill_step_args(e, p, depth, passes, region, hand, a));
+    // Rows both buffers hold (DESIGN §4): a launch of plan 0 writes the field, so it
+    // clears twin_ok; within a step the record says what becomes of twin[].
+    StepLaunch::Twin twin =
+        e->twin_on && e->d_streak && plan == 0 ? StepLaunch::kTwinClear : StepLaunch::kTwinNone;
+    if (rec) {
+        if (plan != 0 || (rec->act && !e->d_streak) || depth != rec->depth || passes != rec->passes)
+            return fail(GOL_ESTATE, "a step's record before a launch that is not the step's");
+        fill_activity_args(e, p, *rec, a);
+        twin = rec->twin;
+        // copy pass, else the calm kernel alone; probe pass
+        if (rec->copy_pass) GOL_TRY(issue_copy_pass(e, p, *rec, a, s));
+        if (rec->calm_alone) GOL_TRY(issue_calm_alone(e, p, a, s));
+        if (rec->probe_pass) GOL_TRY(issue_probe_pass(e, p, *rec, a, s));
+    }
+    // after the probe pass, which reads the flag as the step before left it
+    if (twin == StepLaunch::kTwinClear) GOL_TRY(twin_clear(e, s));
     hipEvent_t e0, e1;
     GOL_TRY(timing_begin(e, s, &e0, &e1));
     // Short step: everything around the launch has happened as in the full
     // step, the calm kernel for twin[] before a last depth-K launch included; the
-    // stencil kernel, which would exit on one load, is left out
-    // (step_single_launches puts one node in place of all of them).
-    if (e->short_skip) {
-        if (!short_ok || e0 || s != e->stream)
+    // stencil kernel, which would exit on one load, is left out (the step puts one
+    // node in place of all of them).
+    if (skip_stencil) {
+        if (!rec || !rec->short_ok || !a.busy || e0 || s != e->stream)
             return fail(GOL_ESTATE, "short step over a launch without the one-load exit");
     } else {
         HIP_TRY(gol::launch_life(a, (int)depth, e->rule, e->planes, hand, s));
     }
-    if (e0) {
-        // cell-generations the lanes actually process: every stage of a block
-        // computes its rows, a classic block (and the last block of a hand-off
-        // segment) also d(d-1) stage-rows of vertical halo, and every strip also
-        // its 2 halo lanes
-        double comp = 0;
-        for (const auto& sg : p.segs) {
-            const double n = (double)std::max<int64_t>(0, sg.out_hi - sg.out_lo);
-            const double classic = hand ? (double)std::min<int64_t>(1, sg.nblk) : (double)sg.nblk;
-            comp += depth * n + classic * depth * (depth - 1.0);
-        }
-        // (the half strip's units: 64 lanes over one block's rows each, classic)
-        double comp_half = 0;
-        for (size_t i = 0; i + 2 < p.pairs.size(); i += 3)
-            comp_half += depth * (double)p.pairs[i + 2] + depth * (depth - 1.0);
-        const double cols = 64.0 * 32.0 * e->planes;  // per strip or unit
-        double rows = 0;
-        for (const auto& sg : p.segs) rows += (double)std::max<int64_t>(0, sg.out_hi - sg.out_lo);
-        GOL_TRY(timing_end(e, s, e0, e1, p.own_rows * (double)e->W * depth * passes,
-                           (comp * p.groups + comp_half) * cols * passes, rows * passes));
-    }
-    if (twin_held) {
+    if (e0) GOL_TRY(timing_end_launch(e, s, e0, e1, p, depth, passes, hand));
+    // the step's only launch, which probes and writes held[] for every unit: twin[] is
+    // held[], copied behind the launch
+    if (twin == StepLaunch::kTwinHeld) {
         const ActState st{e->d_streak, (size_t)e->act_units};
         HIP_TRY(gol::launch_twin_held(a.held, st.twin(), st.twin_ok(), (int32_t)p.total_units, s));
     }
@@ -1565,335 +1588,6 @@ gol_status gol_init_random(gol_engine* e, uint64_t seed)
     return GOL_OK;
 }
 
-}  // extern "C"
-
-namespace golh __attribute__((visibility("hidden"))) {
-
-
-// Passes of the next launch of plan `plan` at depth d with `left` generations to
-// go: multi-pass plans run up to npass full-depth passes per launch.
-int passes_for(const gol_engine* e, int plan, uint32_t d, uint64_t left)
-{
-    const int np = e->plans[(size_t)plan].npass;
-    if (np <= 1 || d != e->K) return 1;
-    return (int)std::min<uint64_t>((uint64_t)np, left / d);
-}
-
-// Fixed step: what a step of `generations` generations at depth K does to
-// the activity state when it starts with twin_ok == 1 and twin[u] == 2 for every unit,
-// every switch of the activity skip on.  The loop is step_single_launches' (pick_depth,
-// act_last), the branches are launch()'s; every unit goes the same way through every
-// kernel, so one record serves all of them.  False: not a short step's shape.
-static bool still_effect(uint32_t K, uint64_t generations, gol_still_effect* out)
-{
-    gol_still_effect fx{};
-    if (K == 0 || pick_depth(K, K) != K) return false;
-    const uint64_t nK = generations / K;
-    if (nK < 5 || nK - 3 > 0xFFFFFFFFull) return false;
-    uint64_t left = generations;
-    int hist = -1;  // launch(): act_hist, the streak parity the last depth-K launch wrote
-    for (uint64_t i = 0; left > 0; ++i) {
-        const uint32_t d = pick_depth(K, left);
-        const bool last = left == d;  // act_last (one pass per launch)
-        if (d == K && i == 0) {
-            // First launch: no history, it probes.  The probe pass before it zeroes
-            // moved[] (life_probe.hip life_probe_zero_kernel); every owned tile has
-            // owners with twin == 2 under twin_ok and takes the sure-tile exit, which
-            // adds 1 to kept[tile] and to sure[tile] and touches nothing else
-            // (life_probe.hip:89-95), so moved[] stays 0.
-            fx.moved = 0;
-            fx.kept_passes += 1;
-            fx.sure_passes += 1;
-            // The launch: every unit that goes on writes busy[1] = launch_idx + 1 = 1
-            // (life_stencil.h:564), finds moved[unit] == 0 and takes the quiet exit
-            // (:902-908): streak_out = min(0 + 1, cap) in streak(1), computed, probed
-            // and pass_probed + 1, held = 1.
-            fx.busy1 = 1;
-            fx.streak1 = 1;
-            fx.computed += 1;
-            fx.probed += 1;
-            fx.pass_probed += 1;
-            fx.held = 1;
-            hist = 1;
-        } else if (d == K && i == 1) {
-            // Second launch, behind the copy pass.  life_calm_kernel: every list entry
-            // has streak(1) == 1, so calm and not still; held[unit] is 1, so the
-            // destination holds the rows: need = 0, elided + 1.  No tile has need: the
-            // tile kernel writes nothing.  The launch: busy[1] == 1 is not below its
-            // index, the lists say calm, not still: busy[1] = 2 (:564) and the
-            // copy-through exit with `through` == 2 (:844-846): streak_out = 1 + 1 in
-            // streak(0), computed + 1, copied + 1.
-            fx.need = 0;
-            fx.elided += 1;
-            fx.busy1 = 2;
-            fx.streak0 = 2;
-            fx.computed += 1;
-            fx.copied += 1;
-            hist = 0;
-        } else if (d == K && i == 2) {
-            // Third launch: busy[1] == 2 is not below 2; every list entry has
-            // streak(0) == 2: the unit skips (:555-560), streak_out = 2 + 1 in
-            // streak(1), skipped + 1.  Nobody writes busy[1].
-            fx.streak1 = 3;
-            fx.skipped += 1;
-            hist = 1;
-        } else if (d == K) {
-            // Launches 4 .. n: busy[1] == 2 < launch_idx >= 3, the one-load exit
-            // (:540-543): busy[0] + 1, no streak written (the short graph's span kernel
-            // adds them up in one go).  launch() still alternates the parity.
-            // All of them at once.
-            const uint64_t more = nK - 1 - i;
-            fx.busy0_add += (uint32_t)(more + 1);
-            fx.launches += more;
-            left -= more * K;
-            i += more;
-            hist = (int)(i & 1) ^ 1;
-            // the step's last launch: life_calm_kernel alone (launch_twin_flags), calm
-            // on streaks of 2 or 3, twin_val 1
-            if (left == K) {
-                fx.twin = 1;
-                fx.twin_ok = 1;
-            }
-        } else {
-            // A remainder launch, behind the copy pass on the streaks `hist` names (2
-            // or 3 everywhere).  life_calm_kernel: calm and still, so need = 0 and
-            // elided + 1 (from the second remainder launch on all_held says the same
-            // and the tile kernel is left out); before the step's last launch twin = 2
-            // (sure tiles) and twin_ok = 1.  The launch has no busy[] and no
-            // streak_out: it neither takes the one-load exit nor skips, and every
-            // unit copies through with `through` == 2 (:844-846): computed + 1,
-            // copied + 1, no streak written.
-            if (hist < 0) return false;
-            fx.need = 0;
-            fx.elided += 1;
-            fx.computed += 1;
-            fx.copied += 1;
-            if (last) {
-                fx.twin = 2;
-                fx.twin_ok = 1;
-            }
-        }
-        fx.launches += 1;
-        left -= d;
-    }
-    *out = fx;
-    return true;
-}
-
-// Single-stream engines: the launch sequence of gol_step(gens) as a captured
-// hipGraph, replayed from the second call on (LRU cache keyed by gens and the
-// starting buffer).
-static gol_status step_single_launches(gol_engine* e, uint64_t generations);
-
-gol_status step_single(gol_engine* e, uint64_t generations)
-{
-    if (e->res.on) return step_resident(e, generations);
-    // (activity skip) the launches issued or captured below are one step's: launch()
-    // numbers them from 0
-    e->act_launch = 0;
-    e->act_hist = -1;
-    e->act_probed = false;
-    e->act_rem = 0;
-    e->act_last = false;
-    e->twin_fresh = true;  // (short step) twin[] may change: gol_sync looks again
-    const gol_status st = step_single_launches(e, generations);
-    e->short_skip = false;
-    e->act_launch = -1;
-    e->act_hist = -1;
-    e->act_probed = false;
-    e->act_rem = 0;
-    e->act_last = false;
-    // a step that failed half-way leaves no statement about the buffers
-    if (st != GOL_OK) (void)twin_clear(e);
-    // (fixed step, GOL_DEV_FIXED_STEP=2) depth-K launches, then a remainder launch
-    e->rem_ended = st == GOL_OK && generations > (uint64_t)e->K && generations % (uint64_t)e->K != 0;
-    return st;
-}
-
-static gol_status step_single_launches(gol_engine* e, uint64_t generations)
-{
-    uint64_t left = generations;
-    const bool graphable = e->timing_every == 0 && generations >= 4 * (uint64_t)e->K;
-    // Short step: the host knows the field is a fixed point (still_seen; or
-    // GOL_DEV_SHORT_STEP=2) and the step has n >= 5 depth-K launches.  Launch 1 takes
-    // the quiet exit, launch 2 is calm, launch 3 skips on the lists and launches 4 .. n
-    // take the one-load exit: the short graph leaves those n - 3 stencil kernels out
-    // and puts one node in their place.  The graph cache's key gains the bit.
-    const uint64_t nK = generations / (uint64_t)e->K;  // pick_depth: depth K while it fits
-    const bool shorty = graphable && e->twin_on && e->still_on && e->d_streak && e->d_err &&
-                        e->plans[0].npass <= 1 && pick_depth(e->K, e->K) == e->K && nK >= 5 &&
-                        nK - 3 <= 0xFFFFFFFFull &&
-                        (e->short_on == 2 || (e->short_on == 1 && e->still_seen));
-    // Fixed step: the short step's conditions (but for its unseen mode), and
-    // the host knows that twin[] holds 2.  One kernel, launched directly: no capture,
-    // no graph.  It repeats the proof on the device; where that fails it writes
-    // nothing but the error word, and the next gol_sync reports it (check_err).
-    const bool shape = graphable && e->fixed_on && e->twin_on && e->still_on && e->d_streak &&
-                       e->d_err && e->plans[0].npass <= 1 && nK >= 5 && nK - 3 <= 0xFFFFFFFFull;
-    if (shape && ((e->fixed_on == 1 && e->short_on == 1 && e->still_seen && e->twin_two) ||
-                  (e->fixed_on == 2 && e->rem_ended))) {
-        gol_still_effect fx;
-        if (!still_effect(e->K, generations, &fx))
-            return fail(GOL_ESTATE, "fixed step: not a short step's shape");
-        const ActState st{e->d_streak, (size_t)e->act_units};
-        gol::StillArgs a{};
-        a.streak0 = st.streak(0);
-        a.streak1 = st.streak(1);
-        a.act = st.act();
-        a.copied = st.copied();
-        a.busy = st.busy();
-        a.probed = st.probed();
-        a.need = st.need();
-        a.held = st.held();
-        a.elided = st.elided();
-        a.moved = st.moved();
-        a.pass_probed = st.pass_probed();
-        a.twin = st.twin();
-        a.twin_ok = st.twin_ok();
-        a.err = e->d_err;
-        a.total_units = (uint32_t)e->plans[0].total_units;
-        a.act_units = (uint32_t)std::min<int64_t>(e->act_units, 0xFFFFFFFFll);
-        a.computed = fx.computed;
-        a.skipped = fx.skipped;
-        a.n_copied = fx.copied;
-        a.n_probed = fx.probed;
-        a.n_pass_probed = fx.pass_probed;
-        a.n_elided = fx.elided;
-        a.busy0_add = fx.busy0_add;
-        a.busy1 = fx.busy1;
-        a.v_streak0 = fx.streak0;
-        a.v_streak1 = fx.streak1;
-        a.v_need = fx.need;
-        a.v_held = fx.held;
-        a.v_moved = fx.moved;
-        a.v_twin = fx.twin;
-        a.v_twin_ok = fx.twin_ok;
-        HIP_TRY(gol::launch_still_step(a, e->stream));
-        // every launch swaps the buffers, which hold the same field
-        e->cur = (int)(((uint64_t)e->cur + fx.launches) % (uint64_t)e->nbuf);
-        ++e->short_steps;
-        ++e->fixed_steps;
-        e->fixed_passes += fx.kept_passes;  // (= sure_passes: one probe pass, all sure)
-        e->twin_two = e->twin_two && fx.twin == 2;
-        return GOL_OK;
-    }
-    // any other step keeps the host's word on twin[] only where it replays a short graph
-    // that ends with a remainder launch, which writes the 2s again
-    e->twin_two = e->twin_two && shorty && generations % (uint64_t)e->K != 0;
-    if (graphable) {
-        const auto key = std::make_pair(generations, e->cur | (shorty ? 0x100 : 0));
-        auto it = e->graphs.find(key);
-        if (it == e->graphs.end()) {
-            if (e->graphs.size() >= kGraphCache) {
-                auto lru = e->graphs.begin();
-                for (auto j = e->graphs.begin(); j != e->graphs.end(); ++j)
-                    if (j->second.used < lru->second.used) lru = j;
-                HIP_TRY(hipStreamSynchronize(e->stream));
-                (void)hipGraphExecDestroy(lru->second.exec);
-                e->graphs.erase(lru);
-            }
-            hipGraph_t g = nullptr;
-            HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-            const int cur0 = e->cur;
-            gol_status st = GOL_OK;
-            // the host flag as it stands: nothing issued while capturing touches the field
-            const bool seen0 = e->still_seen, two0 = e->twin_two;
-            for (uint64_t i = 0; left > 0 && st == GOL_OK; ++i) {
-                const uint32_t d = pick_depth(e->K, left);
-                const int np = passes_for(e, 0, d, left);
-                e->act_last = left == (uint64_t)d * np;
-                e->short_skip = shorty && d == e->K && i >= 3;
-                st = launch(e, 0, d, true, nullptr, np);
-                if (st == GOL_OK && e->short_skip && i == 3) {
-                    const ActState as{e->d_streak, (size_t)e->act_units};
-                    if (gol::launch_still_span(as.busy(), e->d_err, 3u, (uint32_t)(nK - 3), e->stream) !=
-                        hipSuccess)
-                        st = fail(GOL_EHIP, "short step: the span kernel did not launch");
-                }
-                left -= (uint64_t)d * np;
-            }
-            e->short_skip = false;
-            e->still_seen = seen0;
-            e->twin_two = two0;
-            const hipError_t ce = hipStreamEndCapture(e->stream, &g);
-            if (st != GOL_OK) {
-                if (g) (void)hipGraphDestroy(g);
-                e->cur = cur0;
-                return st;
-            }
-            if (ce != hipSuccess) {
-                e->cur = cur0;
-                return fail(GOL_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-            }
-            hipGraphExec_t x = nullptr;
-            const hipError_t ie = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (ie != hipSuccess) {
-                e->cur = cur0;
-                return fail(GOL_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-            }
-            it = e->graphs.emplace(key, gol_engine::GraphEntry{x, e->cur, 0}).first;
-            e->cur = cur0;
-        }
-        it->second.used = ++e->graph_clock;
-        HIP_TRY(hipGraphLaunch(it->second.exec, e->stream));
-        e->cur = it->second.cur_after;
-        if (shorty) ++e->short_steps;
-        return GOL_OK;
-    }
-    while (left > 0) {
-        const uint32_t d = pick_depth(e->K, left);
-        const int np = passes_for(e, 0, d, left);
-        e->act_last = left == (uint64_t)d * np;
-        GOL_TRY(launch(e, 0, d, true, nullptr, np));
-        left -= (uint64_t)d * np;
-    }
-    return GOL_OK;
-}
-
-// Short step, the observation: with the engine's stream idle, gol_sync
-// reads twin[] and twin_ok (they lie one after the other, act_units + 1 words) where a
-// step has run since it last looked.  twin_ok set and a 2 in every unit's word: every
-// unit was calm in the remainder launch that ended the last step, so the whole field
-// equals its generation before, and stays so until somebody writes it.  The words
-// come into pinned memory together with the error word, behind the stream's work, so
-// that gol_sync waits once and issues no blocking copy.
-static bool observe_wanted(const gol_engine* e)
-{
-    // (fixed step) ... and where the field is known still but not that twin[] holds 2
-    const bool news = !e->still_seen || (e->fixed_on == 1 && !e->twin_two);
-    return e->short_on == 1 && e->sync_host && news && e->twin_fresh && e->d_streak &&
-           !e->plans.empty() && e->plans[0].total_units > 0 &&
-           e->plans[0].total_units <= e->act_units;
-}
-
-static gol_status sync_observing(gol_engine* e)
-{
-    const ActState st{e->d_streak, (size_t)e->act_units};
-    const bool look = observe_wanted(e);
-    uint32_t* host = e->sync_host;
-    host[0] = 0;
-    HIP_TRY(hipMemcpyAsync(host, e->d_err, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    if (look)
-        HIP_TRY(hipMemcpyAsync(host + 1, st.twin(), (st.units + 1) * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (host[0]) return check_err(e);
-    if (!look) return GOL_OK;
-    e->twin_fresh = false;
-    const uint32_t* twin = host + 1;
-    if (twin[st.units] == 0) return GOL_OK;
-    const size_t units = (size_t)e->plans[0].total_units;
-    for (size_t u = 0; u < units; ++u)
-        if (twin[u] != 2u) return GOL_OK;
-    e->still_seen = true;
-    e->twin_two = true;  // (fixed step) until a step ends with a depth-K launch
-    return GOL_OK;
-}
-
-}  // namespace golh
-
-extern "C" {
 
 gol_status gol_step(gol_engine* e, uint64_t generations)
 {
@@ -2187,51 +1881,6 @@ static gol_status rect_bounds(const gol_engine* e, uint64_t y, uint64_t x, uint6
                                 std::to_string(e->W) + (e->inner ? " torus" : " field"));
 }
 
-// The activity counters of an engine, summed over its units (and over the parts
-// of a composite engine), after everything issued on its stream has run.
-struct ActTotals {
-    uint64_t computed = 0, skipped = 0, copied = 0, probed = 0, elided = 0, pass_probed = 0;
-    uint64_t pass_kept = 0;  // probe-pass tiles that left their rows (gol_engine::d_kept)
-    uint64_t pass_sure = 0;  // ... of them, those that left before their field loads (d_sure)
-};
-static gol_status read_activity(gol_engine* e, ActTotals& t)
-{
-    if (e->inner) return read_activity(e->inner, t);
-    for (auto* part : e->parts) GOL_TRY(read_activity(part, t));
-    if (!e->parts.empty() || !e->d_streak) return GOL_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const ActState dev{e->d_streak, (size_t)e->act_units};
-    std::vector<uint32_t> host(dev.words());
-    HIP_TRY(hipMemcpy(host.data(), dev.base, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const ActState st{host.data(), dev.units};
-    for (size_t u = 0; u < st.units; ++u) {
-        t.computed += st.act()[2 * u];
-        t.skipped += st.act()[2 * u + 1];
-        t.copied += st.copied()[u];
-        t.probed += st.probed()[u];
-        t.elided += st.elided()[u];
-        t.pass_probed += st.pass_probed()[u];
-    }
-    // launches that every unit skipped at the one-load exit (only plan 0's
-    // launches of a step ever skip)
-    if (!e->plans.empty()) t.skipped += (uint64_t)st.busy()[0] * (uint64_t)e->plans[0].total_units;
-    if (e->d_kept && e->kept_tiles > 0) {
-        std::vector<uint32_t> kept((size_t)e->kept_tiles);
-        HIP_TRY(hipMemcpy(kept.data(), e->d_kept, kept.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (uint32_t k : kept) t.pass_kept += k;
-        if (e->d_sure) {
-            HIP_TRY(hipMemcpy(kept.data(), e->d_sure, kept.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            for (uint32_t k : kept) t.pass_sure += k;
-        }
-    }
-    // (fixed step) its probe passes, each of which would have counted every owned tile
-    // in both arrays
-    t.pass_kept += e->fixed_passes * (uint64_t)e->owned_tiles;
-    if (e->d_sure) t.pass_sure += e->fixed_passes * (uint64_t)e->owned_tiles;
-    return GOL_OK;
-}
-
 // The plan that the gol_plan_* getters and gol_info describe, and in `e` the
 // engine that owns it: the inner engine of a torus, the first part of a composite
 // engine; of a rank engine plans[Hx - 1], the full-round launch over its own rows
@@ -2352,6 +2001,7 @@ gol_status gol_set_timing(gol_engine* e, int every)
     }
     if (every < 0) return fail(GOL_EINVAL, "timing sample interval must be >= 0");
     e->timing_every = (uint32_t)every;
+    e->traits.timing_every = e->timing_every;  // the one trait of a step that changes after create
     e->launch_count = 0;
     return GOL_OK;
 }
@@ -2443,109 +2093,6 @@ gol_status gol_reset_timing(gol_engine* e)
     e->short_steps = 0;
     e->fixed_steps = 0;
     e->fixed_passes = 0;
-    return GOL_OK;
-}
-
-gol_status gol_activity_probed(gol_engine* e, uint64_t* probed_units)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    ActTotals t;
-    GOL_TRY(read_activity(e, t));
-    if (probed_units) *probed_units = t.probed;
-    return GOL_OK;
-}
-
-gol_status gol_activity_pass_probed(gol_engine* e, uint64_t* pass_probed_units)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    ActTotals t;
-    GOL_TRY(read_activity(e, t));
-    if (pass_probed_units) *pass_probed_units = t.pass_probed;
-    return GOL_OK;
-}
-
-gol_status gol_activity_pass_kept(gol_engine* e, uint64_t* kept_tiles)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    ActTotals t;
-    GOL_TRY(read_activity(e, t));
-    if (kept_tiles) *kept_tiles = t.pass_kept;
-    return GOL_OK;
-}
-
-gol_status gol_activity_pass_sure(gol_engine* e, uint64_t* sure_tiles)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    ActTotals t;
-    GOL_TRY(read_activity(e, t));
-    if (sure_tiles) *sure_tiles = t.pass_sure;
-    return GOL_OK;
-}
-
-gol_status gol_activity_short_steps(gol_engine* e, uint64_t* steps)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    // a host count: torus, composite, rank, group and resident engines never arm it
-    if (steps) *steps = (e->inner || !e->parts.empty()) ? 0 : e->short_steps;
-    return GOL_OK;
-}
-
-gol_status gol_activity_fixed_steps(gol_engine* e, uint64_t* steps)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    // a host count, as gol_activity_short_steps
-    if (steps) *steps = (e->inner || !e->parts.empty()) ? 0 : e->fixed_steps;
-    return GOL_OK;
-}
-
-gol_status gol_activity_state(gol_engine* e, uint32_t* out, size_t cap, size_t* words)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    if (e->inner || !e->parts.empty() || !e->d_streak)
-        return fail(GOL_ESTATE, "the engine keeps no activity state");
-    const ActState dev{e->d_streak, (size_t)e->act_units};
-    if (words) *words = dev.words();
-    if (!out) return GOL_OK;
-    if (cap < dev.words()) return fail(GOL_EINVAL, "activity state: the buffer is too small");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(out, dev.base, dev.words() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return GOL_OK;
-}
-
-gol_status gol_plan_still_step(uint32_t tb_depth, uint64_t generations, gol_still_effect* out)
-{
-    if (!out) return fail(GOL_EINVAL, "null argument");
-    if (!still_effect(tb_depth, generations, out))
-        return fail(GOL_EINVAL, "not a short step: fewer than 5 launches of a kernel depth");
-    return GOL_OK;
-}
-
-gol_status gol_activity_elided(gol_engine* e, uint64_t* elided_units)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    ActTotals t;
-    GOL_TRY(read_activity(e, t));
-    if (elided_units) *elided_units = t.elided;
-    return GOL_OK;
-}
-
-gol_status gol_activity_copied(gol_engine* e, uint64_t* copied_units)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    ActTotals t;
-    GOL_TRY(read_activity(e, t));
-    if (copied_units) *copied_units = t.copied;
-    return GOL_OK;
-}
-
-gol_status gol_activity(gol_engine* e, uint64_t* computed_units, uint64_t* skipped_units)
-{
-    if (!e) return fail(GOL_EINVAL, "null engine");
-    ActTotals t;
-    GOL_TRY(read_activity(e, t));
-    if (computed_units) *computed_units = t.computed;
-    if (skipped_units) *skipped_units = t.skipped;
     return GOL_OK;
 }
 

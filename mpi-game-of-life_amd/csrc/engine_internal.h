@@ -1,8 +1,11 @@
 // engine_internal.h -- what the host side of libgol.so shares between its
 // translation units: the engine struct, the stripe geometry, the error macros and
 // the internal functions each unit exports to the others.
-//   engine.cpp   C ABI lifecycle, load/store, single-field and resident steps,
-//                launches and timing, digests, region I/O, plan queries
+//   engine.cpp   C ABI lifecycle, load/store, the resident step, launches and
+//                timing, digests, region I/O, plan queries
+//   step.cpp     the single-stream step: its launches from the schedule of
+//                step_plan.h, run or captured; the short and the fixed step and what
+//                gol_sync observes for them; the activity counters' getters
 //   plan.cpp     launch planning: column layout, rows per wavefront, age-skewed
 //                blocks, hand-off vs classic, the plan autotuner
 //   stripes.cpp  multi-GPU stripes: rank geometry and halo rounds, the exchange
@@ -35,6 +38,7 @@
 #include "bitlayout.h"
 #include "life_internal.h"
 #include "rect_blit.h"
+#include "step_plan.h"
 
 namespace golh __attribute__((visibility("hidden"))) {
 
@@ -372,22 +376,15 @@ struct gol_engine {
 
     // Activity skip (life_stencil.h).  d_streak: the device state of
     // act_units units, laid out as ActState says (single-GPU engines with a plan).
-    // act_launch: index of the next stencil launch within the gol_step that is
-    // being issued, -1 outside one: history never outlives a step, so nothing that
-    // touches the field between steps can leave a stale streak.  act_hist: the
-    // streak parity the step's last depth-K launch wrote, -1 while the step has no
-    // history.
+    // What each launch of a gol_step does with it is the schedule's to say
+    // (step_plan.h); the engine keeps no state of a step: history never outlives one,
+    // so nothing that touches the field between steps can leave a stale streak.
     uint32_t* d_streak = nullptr;
     int64_t act_units = 0;
-    int act_launch = -1;
-    int act_hist = -1;
-    // the step's first launch probed and wrote ActState::held for every unit; the
-    // remainder launches of the step issued so far (copy elision)
-    bool act_probed = false;
-    int act_rem = 0;
-    // the launch being issued is the step's last one (step_single_launches sets it):
-    // the one that decides ActState::twin
-    bool act_last = false;
+    // what the schedule reads of this engine (engine.cpp step_traits, made on first
+    // use; gol_set_timing keeps its interval, the one part that changes, in step)
+    golh::StepTraits traits;
+    bool traits_ok = false;
     // what the engine may do, decided at create:
     bool act_on = false;    // skip units at all
     int through_on = 0;     // copy-through: 0 = off, 1 = launches at depth K, 2 = the
@@ -418,12 +415,10 @@ struct gol_engine {
     // short_on: GOL_DEV_SHORT_STEP, 0 = off, 1 = on (needs sure_on, the only writer of
     // 2), 2 = take the short graph wherever the shape allows (the error-code test).
     // twin_fresh: a step ran since gol_sync last read twin[] (into sync_host);
-    // short_skip: launch() does everything but enqueue the stencil kernel; short_steps: steps that replayed
-    // a short graph (gol_activity_short_steps).
+    // short_steps: steps that replayed a short graph (gol_activity_short_steps).
     int short_on = 0;
     bool still_seen = false;
     bool twin_fresh = false;
-    bool short_skip = false;
     uint64_t short_steps = 0;
     uint32_t* sync_host = nullptr;  // pinned, act_units + 2 words: d_err, twin[], twin_ok
     // Fixed step: on a fixed point whose twin[] words the host knows to be 2,
@@ -523,8 +518,16 @@ gol_status host_layout(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
 gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* cfg,
                        const RankGeom* geom);
 gol_status plan_resident(gol_engine* e, const gol_config* cfg);
+// One stencil launch of `plan` and the kernels that go with it.  rec: the launch's
+// record in the schedule of a single-stream step (step.cpp), which says all that the
+// launch does with the activity state; every other caller passes none, and the launch
+// leaves that state alone but for twin_ok, which a launch of plan 0 clears.
+// skip_stencil: everything but the stencil kernel itself (the short graph).
 gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap = true,
-                  hipStream_t stream = nullptr, int passes = 1);
+                  hipStream_t stream = nullptr, int passes = 1, const StepLaunch* rec = nullptr,
+                  bool skip_stencil = false);
+const StepTraits& step_traits(gol_engine* e);
+gol_status step_resident(gol_engine* e, uint64_t generations);
 gol_status get_event(gol_engine* e, hipEvent_t* ev);
 gol_status join_side_streams(gol_engine* e);
 gol_status quiesce(gol_engine* e);
@@ -595,8 +598,15 @@ gol_status torus_density(gol_engine* e, uint64_t y, uint64_t x, uint64_t rh, uin
 // ---- snapshot.cpp
 void snapshot_free(gol_engine* e);
 
+// ---- step.cpp
+gol_status step_single(gol_engine* e, uint64_t generations);
+gol_status sync_observing(gol_engine* e);
+
 // ---- stripes.cpp
-uint32_t pick_depth(uint32_t K, uint64_t remaining);
+inline uint32_t pick_depth(uint32_t K, uint64_t remaining)
+{
+    return pick_depth(gol::kDepthList, (int)std::size(gol::kDepthList), K, remaining);
+}
 void step_schedule(uint32_t K, uint64_t Hx, bool overlap, bool halo_fresh, uint64_t gens,
                    std::vector<SchedOp>& ops);
 gol_status step_stripe(gol_engine* e, uint64_t generations);

@@ -101,10 +101,10 @@ __global__ __launch_bounds__(64) void life_still_span_kernel(uint32_t* busy, int
 
 // The fixed step (DESIGN §4 "Fixed step"): one workgroup, strided over the units, in
 // place of every kernel of a step that starts on a proven fixed point.  Phase 1 is the
-// proof itself, as gol_sync makes it on the host (engine.cpp sync_observing): twin_ok
+// proof itself, as gol_sync makes it on the host (step.cpp sync_observing): twin_ok
 // set and a 2 in every unit's word.  Phase 2, behind the barrier that reduces phase 1,
 // adds the step's increments and stores its final values, none of which depends on what
-// a word held (engine.cpp still_effect derives them from the kernels).  Where the proof
+// a word held (step.cpp still_effect derives them from the kernels).  Where the proof
 // fails one lane stores kErrShortStep and nothing else is written.  Plain vector loads
 // and stores by one workgroup: no atomics, no scratch, no field word touched.
 // Every index is below min(total_units, act_units), the length of every region.

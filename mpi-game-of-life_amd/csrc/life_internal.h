@@ -301,7 +301,7 @@ hipError_t launch_still_span(uint32_t* busy, int* err, uint32_t first_idx, uint3
 // The fixed step (DESIGN §4 "Fixed step"): one workgroup in place of every kernel of a
 // step on a proven fixed point.  The proof is *twin_ok != 0 and twin[u] == 2 for every
 // unit; where it holds the kernel adds the step's increments to the counters and
-// stores its final values to the state words (engine.cpp still_effect computes both),
+// stores its final values to the state words (step.cpp still_effect computes both),
 // else it stores kErrShortStep to *err and nothing else.  The regions are ActState's
 // (engine_internal.h), each of act_units words (act: 2 per unit), of which the first
 // total_units are touched.

@@ -144,13 +144,6 @@ gol_status rank_geometry(uint64_t h, const gol_config* cfg, int rank, int nranks
     return GOL_OK;
 }
 
-uint32_t pick_depth(uint32_t K, uint64_t remaining)
-{
-    for (int d : gol::kDepthList)
-        if ((uint32_t)d <= K && (uint64_t)d <= remaining) return (uint32_t)d;
-    return 1;
-}
-
 // The launches of one round of `round` generations after a halo exchange: each
 // launch of depth d shrinks the valid region by d rows per side (plan c-1 for a
 // cumulative shrink of c).  With overlap, the last launch of a full round runs

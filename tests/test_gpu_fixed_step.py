@@ -1,4 +1,4 @@
-"""GPU: on a proven fixed point a step is one kernel (engine.cpp step_single_launches,
+"""GPU: on a proven fixed point a step is one kernel (step.cpp step_single_launches,
 life_copy.hip life_still_step_kernel, DESIGN §4 "Fixed step"), next to the same engine
 with GOL_DEV_FIXED_STEP=0 (the short graph, 11 kernels) and with GOL_DEV_SHORT_STEP=0
 (every kernel of the step), against the CPU oracle.

@@ -1,5 +1,5 @@
 """GPU: a step that the host knows starts from a fixed point replays a short graph
-(engine.cpp step_single_launches, DESIGN §4 "Short step"), next to the same engine with
+(step.cpp step_single_launches, DESIGN §4 "Short step"), next to the same engine with
 GOL_DEV_SHORT_STEP=0, against the CPU oracle.
 
 gol_sync reads twin[] where a step has run since it last looked.  twin_ok set and a 2
