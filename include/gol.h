@@ -204,7 +204,12 @@ gol_status gol_init_random(gol_engine* e, uint64_t seed);
 
 /* Replaces the epoch loop (:215-221): advances `generations` generations
  * (including the halo exchange of a rank engine).  Returns after the work is
- * enqueued; gol_sync() waits for it. */
+ * enqueued; gol_sync() waits for it.
+ * A fixed step (below, gol_activity_fixed_steps) may enqueue nothing: its one kernel is
+ * launched by the next call that looks at the activity state or the error word or
+ * enqueues work that does, gol_sync among them, and stands for every fixed step since
+ * the last such call.  If that kernel does not launch, the status (GOL_EHIP) is that
+ * call's, not gol_step's. */
 gol_status gol_step(gol_engine* e, uint64_t generations);
 gol_status gol_sync(gol_engine* e);
 
@@ -323,7 +328,17 @@ gol_status gol_activity_short_steps(gol_engine* e, uint64_t* steps);
  * count; they count in gol_activity_short_steps as well).  GOL_DEV_FIXED_STEP=0 at
  * create turns the path off (the short graph runs instead), as does whatever turns
  * the short step off; GOL_DEV_FIXED_STEP=2 takes it after every step that ended with
- * a remainder launch, seen or not (tests of the error status only). */
+ * a remainder launch, seen or not (tests of the error status only).
+ * Pending fixed steps: consecutive fixed steps do not interact on the device (the
+ * increments add up modulo 2^32, the final values are the last step's), so gol_step
+ * only books them on the host, and one kernel with the sums runs when a call needs
+ * the state: gol_sync, every gol_activity_* getter that reads the device,
+ * gol_activity_state, gol_reset_timing, a step that is not fixed, every writer of the
+ * field, a snapshot comparison, and whatever checks the error word after its own work
+ * (digests, stores, rectangle reads).  gol_activity_fixed_launches: launches of that
+ * kernel since create or gol_reset_timing (a host count): with n fixed steps between
+ * two such calls it grows by 1, by n with GOL_DEV_FIXED_DEFER=0 at create, which
+ * launches one kernel per fixed step. */
 typedef struct gol_still_effect {
     uint64_t launches;    /* stencil launches the step stands for (the buffers swap per launch) */
     /* added to every unit's counter */
@@ -337,6 +352,7 @@ typedef struct gol_still_effect {
 } gol_still_effect;
 gol_status gol_plan_still_step(uint32_t tb_depth, uint64_t generations, gol_still_effect* out);
 gol_status gol_activity_fixed_steps(gol_engine* e, uint64_t* steps);
+gol_status gol_activity_fixed_launches(gol_engine* e, uint64_t* launches);
 
 /* The activity state as it lies on the device, after everything enqueued has run:
  * 12 * units + 3 words (engine_internal.h ActState names the regions), for tests that

@@ -42,7 +42,8 @@ EXPORTS = [
     "gol_activity_copied", "gol_activity_probed", "gol_activity_elided", "gol_torus_geometry", "gol_torus_pad",
     "gol_activity_pass_probed", "gol_plan_probe_tiles", "gol_activity_pass_kept",
     "gol_activity_pass_sure", "gol_activity_short_steps",
-    "gol_plan_still_step", "gol_activity_fixed_steps", "gol_activity_state",
+    "gol_plan_still_step", "gol_activity_fixed_steps", "gol_activity_fixed_launches",
+    "gol_activity_state",
     "gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit",
     "gol_snapshot", "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
     "gol_snapshot_drop", "gol_step_until_periodic",
@@ -285,6 +286,7 @@ def lib():
     L.gol_activity_pass_sure.argtypes = [vp, pu64]
     L.gol_activity_short_steps.argtypes = [vp, pu64]
     L.gol_activity_fixed_steps.argtypes = [vp, pu64]
+    L.gol_activity_fixed_launches.argtypes = [vp, pu64]
     L.gol_activity_state.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.gol_plan_still_step.argtypes = [u32, u64, ctypes.POINTER(StillEffect)]
     L.gol_plan_probe_tiles.argtypes = [u64, u64, ctypes.POINTER(Config), i32, i32, i32, vp, u64,
@@ -344,7 +346,8 @@ def lib():
                  "gol_activity_elided", "gol_activity_pass_probed", "gol_plan_probe_tiles",
                  "gol_activity_pass_kept", "gol_activity_pass_sure",
                  "gol_activity_short_steps", "gol_plan_still_step",
-                 "gol_activity_fixed_steps", "gol_activity_state"]:
+                 "gol_activity_fixed_steps", "gol_activity_fixed_launches",
+                 "gol_activity_state"]:
         getattr(L, name).restype = ctypes.c_int
     _lib = L
     return L
@@ -815,6 +818,14 @@ class Engine:
         every unit calm (gol_activity_fixed_steps; a host count)."""
         c = ctypes.c_uint64()
         _check(lib().gol_activity_fixed_steps(self._h, ctypes.byref(c)))
+        return c.value
+
+    def activity_fixed_launches(self):
+        """Launches of the fixed step's kernel: one for every run of fixed steps with no
+        look at the activity state between them, one per step with GOL_DEV_FIXED_DEFER=0
+        (gol_activity_fixed_launches; a host count)."""
+        c = ctypes.c_uint64()
+        _check(lib().gol_activity_fixed_launches(self._h, ctypes.byref(c)))
         return c.value
 
     def activity_state(self):

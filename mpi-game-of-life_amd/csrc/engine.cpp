@@ -379,6 +379,10 @@ gol_status init_common(gol_engine* e, uint64_t h, uint64_t w, const gol_config* 
                 if (sg.out_lo < 0 || owned != e->kept_tiles) whole = false;
             }
             e->fixed_on = !whole ? 0 : fv == 2 ? 2 : (fv != 0 && e->short_on == 1) ? 1 : 0;
+            // pending fixed steps: the kernel waits for the next look at the state
+            // (GOL_DEV_FIXED_DEFER=0 = off: one kernel per fixed step)
+            const char* fd = std::getenv("GOL_DEV_FIXED_DEFER");
+            e->defer_on = e->fixed_on != 0 && !(fd && std::atoi(fd) == 0);
         }
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -912,6 +916,8 @@ gol_status launch(gol_engine* e, int plan, uint32_t depth, bool swap, hipStream_
     hipStream_t s = stream ? stream : e->stream;
     const int region = (e->band_stream && s == e->band_stream) ? 1 : 0;
     const auto& p = e->plans[plan];
+    // (a step flushes before it captures; whoever else launches finds steps pending here)
+    GOL_TRY(flush_still(e));
     if (passes < 1 || (passes > 1 && (passes > p.npass || depth != e->K || !e->mpflags)))
         return fail(GOL_ESTATE, "multi-pass launch of a plan without passes");
     const bool hand = launch_hands(e, p, region, depth);
@@ -993,6 +999,8 @@ gol_status twin_clear(gol_engine* e, hipStream_t s)
     // gol_sync saw no longer holds, on whatever stream the write goes
     e->still_seen = false;
     e->twin_two = false;  // (fixed step) twin[] says nothing any more
+    // pending fixed steps prove themselves on the flag as it stands, and write it
+    GOL_TRY(flush_still(e));
     if (!e->d_streak || !e->twin_on) return GOL_OK;  // nobody reads the flag
     const ActState st{e->d_streak, (size_t)e->act_units};
     HIP_TRY(hipMemsetAsync(st.twin_ok(), 0, sizeof(uint32_t), s ? s : e->stream));
@@ -1003,6 +1011,11 @@ gol_status twin_clear(gol_engine* e, hipStream_t s)
 gol_status check_err(gol_engine* e)
 {
     if (!e->d_err) return GOL_OK;
+    // pending fixed steps may write the word: their kernel runs before the look
+    if (e->pending.steps) {
+        GOL_TRY(flush_still(e));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
     int err = 0;
     HIP_TRY(hipMemcpy(&err, e->d_err, sizeof(int), hipMemcpyDeviceToHost));
     if (!err) return GOL_OK;
@@ -1309,6 +1322,7 @@ void gol_destroy(gol_engine* e)
         return;
     }
     (void)hipSetDevice(e->device);
+    e->pending = StillPending{};  // pending fixed steps: nobody is left to look
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->comm_stream) (void)hipStreamSynchronize(e->comm_stream);
     if (e->band_stream) (void)hipStreamSynchronize(e->band_stream);
@@ -1616,6 +1630,7 @@ gol_status gol_sync(gol_engine* e)
     // (short step) a single-stream engine that may arm the short graph: one wait for
     // the work, the error word and, where a step has run, twin[]
     if (e->sync_host && e->d_err && !e->band_stream && !e->comm_stream) return sync_observing(e);
+    GOL_TRY(flush_still(e));  // (GOL_DEV_FIXED_STEP=2 without the short step's look)
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->band_stream) HIP_TRY(hipStreamSynchronize(e->band_stream));
     if (e->comm_stream) HIP_TRY(hipStreamSynchronize(e->comm_stream));
@@ -2072,6 +2087,8 @@ gol_status gol_reset_timing(gol_engine* e)
     e->tm = gol_timing{};
     if (e->d_streak) {
         HIP_TRY(hipSetDevice(e->device));
+        // pending fixed steps count before the reset, and leave their state words
+        GOL_TRY(flush_still(e));
         // Every counter: computed / skipped, copied and busy[0] lie one after the
         // other, the probed ones behind busy[1], the elided ones behind the pass's and
         // the probe's flags, the probe pass's behind its words.  The streaks, the
@@ -2093,6 +2110,7 @@ gol_status gol_reset_timing(gol_engine* e)
     e->short_steps = 0;
     e->fixed_steps = 0;
     e->fixed_passes = 0;
+    e->fixed_launches = 0;
     return GOL_OK;
 }
 

@@ -39,6 +39,7 @@
 #include "life_internal.h"
 #include "rect_blit.h"
 #include "step_plan.h"
+#include "still_pending.h"
 
 namespace golh __attribute__((visibility("hidden"))) {
 
@@ -439,6 +440,18 @@ struct gol_engine {
     uint64_t fixed_steps = 0;
     uint64_t fixed_passes = 0;
     int64_t owned_tiles = 0;
+    // Pending fixed steps (still_pending.h): with defer_on (GOL_DEV_FIXED_DEFER, default
+    // on; 0 = one kernel per step) a fixed step does its host part at once and folds
+    // its effect on the device state into `pending`; flush_still launches the one kernel
+    // that stands for all of them before anybody reads or writes the activity state or
+    // the error word.  fixed_launches: launches of life_still_step_kernel
+    // (gol_activity_fixed_launches).  still_memo: still_effect() of the last length a
+    // fixed step had (still_memo_gens, 0 = none), so that a repeat walks no schedule.
+    bool defer_on = false;
+    golh::StillPending pending;
+    uint64_t fixed_launches = 0;
+    uint64_t still_memo_gens = 0;
+    gol_still_effect still_memo{};
 
     // resident kernel (life_resident.hip): small GLOBAL fields, one launch per
     // gol_step; flags count the epochs published, from flag_base on
@@ -601,6 +614,16 @@ void snapshot_free(gol_engine* e);
 // ---- step.cpp
 gol_status step_single(gol_engine* e, uint64_t generations);
 gol_status sync_observing(gol_engine* e);
+// Pending fixed steps (still_pending.h) reach the device: one life_still_step_kernel on
+// the engine's stream for all of them.  Whoever enqueues work on that stream that reads
+// or writes the activity state or the error word, or reads them on the host, calls this
+// first (DESIGN §4 "Fixed step" lists the callers); with nothing pending it tests one
+// word.  Every caller has made the engine's device the current one.
+gol_status flush_still_launch(gol_engine* e);
+inline gol_status flush_still(gol_engine* e)
+{
+    return e->pending.steps ? flush_still_launch(e) : GOL_OK;
+}
 
 // ---- stripes.cpp
 inline uint32_t pick_depth(uint32_t K, uint64_t remaining)

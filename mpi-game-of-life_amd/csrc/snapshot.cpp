@@ -104,6 +104,7 @@ gol_status compare_begin(const SnapView& v, bool count)
 {
     gol_engine* e = v.leaf;
     HIP_TRY(hipSetDevice(e->device));
+    GOL_TRY(flush_still(e));  // compare_end reads the error word behind this work
     GOL_TRY(join_side_streams(e));
     HIP_TRY(hipMemsetAsync(e->d_acc, 0, 2 * sizeof(unsigned long long), e->stream));
     for (const auto& r : v.regs) {

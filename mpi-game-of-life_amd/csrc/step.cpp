@@ -1,7 +1,8 @@
 // step.cpp -- the single-stream step of libgol.so (engine_internal.h): gol_step on an
 // engine that steps alone, its launches taken from the schedule of step_plan.h and
 // issued one by one or captured into a graph; the short step and the fixed step
-//  with what gol_sync observes for them; the activity counters' getters.
+//  with what gol_sync observes for them; pending fixed steps and their one
+// kernel (still_pending.h, flush_still); the activity counters' getters.
 #include "engine_internal.h"
 
 namespace golh __attribute__((visibility("hidden"))) {
@@ -120,6 +121,61 @@ static bool still_effect(const StepTraits& t, uint64_t generations, gol_still_ef
     return true;
 }
 
+// Pending fixed steps (still_pending.h) reach the device: life_still_step_kernel once,
+// with the increments summed over the steps and the final values of the last one.  It
+// repeats the proof on the state as the first pending step found it; where that fails
+// it writes the error word alone, as each of the steps' kernels would have.  The
+// record is cleared whether or not the kernel launches: a failure is the caller's to
+// report, and what the host believed of twin[] goes with it.
+gol_status flush_still_launch(gol_engine* e)
+{
+    const gol_still_effect fx = e->pending.fx;
+    const bool any = e->pending.steps != 0;
+    e->pending = StillPending{};
+    if (!any) return GOL_OK;
+    const ActState st{e->d_streak, (size_t)e->act_units};
+    gol::StillArgs a{};
+    a.streak0 = st.streak(0);
+    a.streak1 = st.streak(1);
+    a.act = st.act();
+    a.copied = st.copied();
+    a.busy = st.busy();
+    a.probed = st.probed();
+    a.need = st.need();
+    a.held = st.held();
+    a.elided = st.elided();
+    a.moved = st.moved();
+    a.pass_probed = st.pass_probed();
+    a.twin = st.twin();
+    a.twin_ok = st.twin_ok();
+    a.err = e->d_err;
+    a.total_units = (uint32_t)e->plans[0].total_units;
+    a.act_units = (uint32_t)std::min<int64_t>(e->act_units, 0xFFFFFFFFll);
+    a.computed = fx.computed;
+    a.skipped = fx.skipped;
+    a.n_copied = fx.copied;
+    a.n_probed = fx.probed;
+    a.n_pass_probed = fx.pass_probed;
+    a.n_elided = fx.elided;
+    a.busy0_add = fx.busy0_add;
+    a.busy1 = fx.busy1;
+    a.v_streak0 = fx.streak0;
+    a.v_streak1 = fx.streak1;
+    a.v_need = fx.need;
+    a.v_held = fx.held;
+    a.v_moved = fx.moved;
+    a.v_twin = fx.twin;
+    a.v_twin_ok = fx.twin_ok;
+    const hipError_t he = gol::launch_still_step(a, e->stream);
+    if (he != hipSuccess) {
+        (void)twin_clear(e);
+        return fail(GOL_EHIP, std::string("fixed step: the kernel did not launch: ") +
+                                  hipGetErrorString(he));
+    }
+    ++e->fixed_launches;
+    return GOL_OK;
+}
+
 // The step's launches in the schedule's order, on the engine's stream (issued, or
 // captured by the caller).  shorty: the stencil kernels of the depth-K launches from
 // index 3 on are left out, and one span kernel stands behind the first of them.
@@ -156,48 +212,25 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
     const bool shape = short_shape(t, generations);
     const bool shorty = shape && (e->short_on == 2 || (e->short_on == 1 && e->still_seen));
     // Fixed step: the short step's shape, and the host knows that twin[]
-    // holds 2.  One kernel, launched directly: no capture, no graph.  It repeats the
-    // proof on the device; where that fails it writes nothing but the error word, and
-    // the next gol_sync reports it (check_err).
+    // holds 2.  One kernel, launched directly (flush_still_launch): no capture, no graph.
+    // It repeats the proof on the device; where that fails it writes nothing but the
+    // error word, and the next gol_sync reports it (check_err).
     if (shape && ((e->fixed_on == 1 && e->short_on == 1 && e->still_seen && e->twin_two) ||
                   (e->fixed_on == 2 && e->rem_ended))) {
-        gol_still_effect fx;
-        if (!still_effect(t, generations, &fx))
-            return fail(GOL_ESTATE, "fixed step: not a short step's shape");
-        const ActState st{e->d_streak, (size_t)e->act_units};
-        gol::StillArgs a{};
-        a.streak0 = st.streak(0);
-        a.streak1 = st.streak(1);
-        a.act = st.act();
-        a.copied = st.copied();
-        a.busy = st.busy();
-        a.probed = st.probed();
-        a.need = st.need();
-        a.held = st.held();
-        a.elided = st.elided();
-        a.moved = st.moved();
-        a.pass_probed = st.pass_probed();
-        a.twin = st.twin();
-        a.twin_ok = st.twin_ok();
-        a.err = e->d_err;
-        a.total_units = (uint32_t)e->plans[0].total_units;
-        a.act_units = (uint32_t)std::min<int64_t>(e->act_units, 0xFFFFFFFFll);
-        a.computed = fx.computed;
-        a.skipped = fx.skipped;
-        a.n_copied = fx.copied;
-        a.n_probed = fx.probed;
-        a.n_pass_probed = fx.pass_probed;
-        a.n_elided = fx.elided;
-        a.busy0_add = fx.busy0_add;
-        a.busy1 = fx.busy1;
-        a.v_streak0 = fx.streak0;
-        a.v_streak1 = fx.streak1;
-        a.v_need = fx.need;
-        a.v_held = fx.held;
-        a.v_moved = fx.moved;
-        a.v_twin = fx.twin;
-        a.v_twin_ok = fx.twin_ok;
-        HIP_TRY(gol::launch_still_step(a, e->stream));
+        // the effect is a function of the length alone: the last one is kept
+        if (e->still_memo_gens != generations) {
+            gol_still_effect one;
+            if (!still_effect(t, generations, &one))
+                return fail(GOL_ESTATE, "fixed step: not a short step's shape");
+            e->still_memo = one;
+            e->still_memo_gens = generations;
+        }
+        const gol_still_effect& fx = e->still_memo;
+        // Pending steps (still_pending.h): the step's part on the device waits, folded
+        // into the record, until somebody looks (flush_still); GOL_DEV_FIXED_DEFER=0:
+        // at once, one kernel per step.  A kernel that does not launch leaves no step.
+        e->pending = still_accumulate(e->pending, fx);
+        if (!e->defer_on) GOL_TRY(flush_still_launch(e));
         // every launch swaps the buffers, which hold the same field
         e->cur = (int)(((uint64_t)e->cur + fx.launches) % (uint64_t)e->nbuf);
         ++e->short_steps;
@@ -206,8 +239,11 @@ static gol_status step_single_launches(gol_engine* e, uint64_t generations)
         e->twin_two = e->twin_two && fx.twin == 2;
         return GOL_OK;
     }
-    // any other step keeps the host's word on twin[] only where it replays a short graph
-    // that ends with a remainder launch, which writes the 2s again
+    // any other step's kernels read and write the activity state: pending fixed steps
+    // go first, before a capture begins
+    GOL_TRY(flush_still(e));
+    // it keeps the host's word on twin[] only where it replays a short graph that ends
+    // with a remainder launch, which writes the 2s again
     e->twin_two = e->twin_two && shorty && generations % (uint64_t)e->K != 0;
     if (graphable) {
         const auto key = std::make_pair(generations, e->cur | (shorty ? 0x100 : 0));
@@ -288,6 +324,7 @@ static bool observe_wanted(const gol_engine* e)
 
 gol_status sync_observing(gol_engine* e)
 {
+    GOL_TRY(flush_still(e));  // pending fixed steps write the words copied below
     const ActState st{e->d_streak, (size_t)e->act_units};
     const bool look = observe_wanted(e);
     uint32_t* host = e->sync_host;
@@ -323,6 +360,7 @@ static gol_status read_activity(gol_engine* e, ActTotals& t)
     for (auto* part : e->parts) GOL_TRY(read_activity(part, t));
     if (!e->parts.empty() || !e->d_streak) return GOL_OK;
     HIP_TRY(hipSetDevice(e->device));
+    GOL_TRY(flush_still(e));
     HIP_TRY(hipStreamSynchronize(e->stream));
     const ActState dev{e->d_streak, (size_t)e->act_units};
     std::vector<uint32_t> host(dev.words());
@@ -423,6 +461,14 @@ gol_status gol_activity_fixed_steps(gol_engine* e, uint64_t* steps)
     return GOL_OK;
 }
 
+gol_status gol_activity_fixed_launches(gol_engine* e, uint64_t* launches)
+{
+    if (!e) return fail(GOL_EINVAL, "null engine");
+    // a host count, as gol_activity_short_steps
+    if (launches) *launches = (e->inner || !e->parts.empty()) ? 0 : e->fixed_launches;
+    return GOL_OK;
+}
+
 gol_status gol_activity_state(gol_engine* e, uint32_t* out, size_t cap, size_t* words)
 {
     if (!e) return fail(GOL_EINVAL, "null engine");
@@ -433,6 +479,7 @@ gol_status gol_activity_state(gol_engine* e, uint32_t* out, size_t cap, size_t* 
     if (!out) return GOL_OK;
     if (cap < dev.words()) return fail(GOL_EINVAL, "activity state: the buffer is too small");
     HIP_TRY(hipSetDevice(e->device));
+    GOL_TRY(flush_still(e));
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(out, dev.base, dev.words() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return GOL_OK;

@@ -14,7 +14,9 @@ has three depth-16 launches and life_still_span_kernel in place of the others: i
 duration is still_span_us, and launches_per_step counts every kernel of the step.
 A fixed step (DESIGN §4 "Fixed step") is life_still_step_kernel alone: a step of one
 kernel, whose duration is fixed_step_us and the step's span; fixed_steps counts them
-among the steps read.
+among the steps read.  With pending fixed steps a fixed step may have no
+kernel: fixed_launches_in_timed_region counts the kernels behind the last step that was
+not fixed, and kernels_per_timed_step divides them by --steps.
 
     python tools/trace_launches.py TRACE_kernel_trace.csv [--steps 20] [--depth 16]
 """
@@ -98,6 +100,13 @@ def main():
         add("step_span_us", rem[1] - (pp[0][0] if pp else deep[0][0]))
     out = {"steps": len(full), "fixed_steps": sum(1 for st in full if st[-1][2] == "fixed"),
            "launches_per_step": statistics.median(len(st) for st in full)}
+    # Pending fixed steps (DESIGN §4 "Fixed step"): a timed step may have no kernel at
+    # all.  The timed region is what follows the last step that was not a fixed one
+    # (the warm-up's): its kernels over the --steps steps the caller says it held.
+    last_other = max((i for i, st in enumerate(steps) if st[-1][2] != "fixed"), default=-1)
+    tail = steps[last_other + 1:]
+    out["fixed_launches_in_timed_region"] = len(tail)
+    out["kernels_per_timed_step"] = round(sum(len(st) for st in tail) / a.steps, 3)
     out.update({k: round(statistics.median(v), 2) for k, v in cols.items()})
     print(json.dumps(out, indent=1))
 
