@@ -559,7 +559,8 @@ gol_status gol_step_until_periodic(gol_engine* e, uint64_t max_generations, uint
                                    uint32_t check_every, uint32_t flags, gol_until* out);
 
 /* ---- Batches: many small independent fields stepped in one launch ----
- * A gol_batch holds n fields of the same h x w, the same rule and the same boundary on
+ * A gol_batch holds n fields of the same h x w, the same rule (or, after
+ * gol_batch_set_rules, a rule per field) and the same boundary on
  * one device and advances all of them with one kernel launch per step: a lane holds a
  * 64-column word of a field and all its rows in registers, so a 64 x 64 field is one
  * lane, a wavefront 64 fields, and between a launch's loads and stores nothing touches
@@ -675,6 +676,38 @@ typedef struct gol_batch_until_plan {
 } gol_batch_until_plan;
 gol_status gol_batch_until_plan_of(uint64_t max_generations, uint32_t lag, uint32_t check_every,
                                    uint32_t launch_generations, gol_batch_until_plan* out);
+
+/* Per-field rules: one launch sweeps many rules.
+ * gol_batch_set_rules gives field first + i the rule (birth[i], survive[i]), 9-bit masks
+ * as gol_config's.  The first call with count > 0 allocates a device table of n words
+ * (birth | survive << 16) in which every field starts with the create rule; a call writes
+ * its range into the table and leaves every other field's rule as it is, so later calls
+ * overwrite only their own range.  While the table exists, gol_batch_step and
+ * gol_batch_step_until_periodic run the kernels that hold a rule per lane for every
+ * field, fields that happen to share one rule included, and each field evolves exactly
+ * as a batch created with that field's rule would.  Loads, stores, gol_batch_init_random,
+ * gol_batch_digest and the geometry are untouched.  The table copy is enqueued on the
+ * batch's stream, behind the steps already enqueued, which therefore still run by the
+ * rules they were enqueued under; like gol_batch_load_packed the call returns once the
+ * caller's arrays have been consumed.  The table is a call of its own and not a create
+ * argument because a rule table is data like the fields: set per range and replaceable
+ * between steps.
+ * GOL_EINVAL: null batch, first + count > n, null birth or survive with count > 0, any
+ * mask above 0x1FF; in each of these cases nothing changes: no table is made and an
+ * existing one is not altered.  count == 0 is GOL_OK with nothing done and nothing
+ * allocated.  GOL_ENOMEM if the table cannot be allocated.  gol_batch_destroy frees it. */
+gol_status gol_batch_set_rules(gol_batch* b, uint64_t first, uint64_t count,
+                               const uint32_t* birth, const uint32_t* survive);
+/* The rule each of the fields [first, first + count) runs: the table's, or the create rule
+ * where none was set.  Either array may be NULL.  GOL_EINVAL: null batch, first + count >
+ * n.  Synchronous like gol_batch_digest. */
+gol_status gol_batch_get_rules(gol_batch* b, uint64_t first, uint64_t count, uint32_t* birth,
+                               uint32_t* survive);
+/* Back to the one rule given at create: waits for the steps enqueued and frees the table.
+ * GOL_OK when there is none. */
+gol_status gol_batch_drop_rules(gol_batch* b);
+/* *on = 1 while the batch steps with per-field rules, else 0.  Host only. */
+gol_status gol_batch_has_rules(gol_batch* b, uint32_t* on);
 
 /* live[i], hash[i] = exactly what gol_digest returns for an h x w engine that holds
  * field first + i (either array may be NULL).  Only 2 * count words cross to the host. */

@@ -51,6 +51,7 @@ EXPORTS = [
     "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
     "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step", "gol_batch_sync",
     "gol_batch_digest", "gol_batch_step_until_periodic", "gol_batch_until_plan_of",
+    "gol_batch_set_rules", "gol_batch_get_rules", "gol_batch_drop_rules", "gol_batch_has_rules",
 ]
 
 # gol_step_until_periodic flag: run on to max_generations once a period is known
@@ -323,11 +324,16 @@ def lib():
     L.gol_batch_step_until_periodic.argtypes = [vp, u64, u32, u32, vp, vp,
                                                 ctypes.POINTER(BatchUntil)]
     L.gol_batch_until_plan_of.argtypes = [u64, u32, u32, u32, ctypes.POINTER(BatchUntilPlan)]
+    L.gol_batch_set_rules.argtypes = [vp, u64, u64, vp, vp]
+    L.gol_batch_get_rules.argtypes = [vp, u64, u64, vp, vp]
+    L.gol_batch_drop_rules.argtypes = [vp]
+    L.gol_batch_has_rules.argtypes = [vp, pu32]
     for name in ["gol_batch_geometry", "gol_batch_create", "gol_batch_info",
                  "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
                  "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step",
                  "gol_batch_sync", "gol_batch_digest", "gol_batch_step_until_periodic",
-                 "gol_batch_until_plan_of"]:
+                 "gol_batch_until_plan_of", "gol_batch_set_rules", "gol_batch_get_rules",
+                 "gol_batch_drop_rules", "gol_batch_has_rules"]:
         getattr(L, name).restype = ctypes.c_int
     for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit", "gol_snapshot",
                  "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
@@ -856,8 +862,9 @@ class Engine:
 
 
 class BatchEngine:
-    """n independent h x w fields of one rule and one boundary (SEM_GLOBAL: a dead
-    border per field, SEM_TORUS: a torus per field) on one GPU, advanced together by
+    """n independent h x w fields of one rule (or, after set_rules, one per field) and
+    one boundary (SEM_GLOBAL: a dead border per field, SEM_TORUS: a torus per field) on
+    one GPU, advanced together by
     one launch per step (gol_batch).  Fields are packed uint64 arrays of shape
     [count, h, ceil(w/64)], or contiguous torch.int64 CUDA tensors of that shape."""
 
@@ -976,6 +983,45 @@ class BatchEngine:
                                                    period.ctypes.data, generation.ctypes.data,
                                                    ctypes.byref(r)))
         return BatchPeriods(period, generation, r)
+
+    def set_rules(self, birth, survive, first=0):
+        """Fields [first, first + len(birth)) get the rules (birth[i], survive[i]), 9-bit
+        masks (gol_batch_set_rules).  From the first call on every field steps by the rule
+        table, in which a field not set yet holds the create rule."""
+        import numpy as np
+        try:
+            bm = np.asarray(birth, dtype=np.int64)
+            sm = np.asarray(survive, dtype=np.int64)
+        except (TypeError, ValueError, OverflowError):
+            raise GolError(GOL_EINVAL, "birth and survive must be arrays of 9-bit masks")
+        if bm.ndim != 1 or bm.shape != sm.shape:
+            raise GolError(GOL_EINVAL, "birth and survive must be 1-d arrays of equal length")
+        if ((bm < 0) | (bm > 0x1FF) | (sm < 0) | (sm > 0x1FF)).any():
+            raise GolError(GOL_EINVAL, "rule masks are 9-bit")
+        b = np.ascontiguousarray(bm, dtype=np.uint32)
+        s = np.ascontiguousarray(sm, dtype=np.uint32)
+        _check(lib().gol_batch_set_rules(self._h, first, b.shape[0], b.ctypes.data, s.ctypes.data))
+
+    def rules(self, first=0, count=None):
+        """(birth, survive): two uint32 arrays [count], the rule each field runs (the create
+        rule where none was set; gol_batch_get_rules)."""
+        import numpy as np
+        count = self._count(first, count)
+        b = np.zeros(max(count, 0), dtype=np.uint32)
+        s = np.zeros(max(count, 0), dtype=np.uint32)
+        _check(lib().gol_batch_get_rules(self._h, first, count, b.ctypes.data, s.ctypes.data))
+        return b, s
+
+    def drop_rules(self):
+        """Back to the one rule given at create (gol_batch_drop_rules)."""
+        _check(lib().gol_batch_drop_rules(self._h))
+
+    @property
+    def per_field_rules(self):
+        """True while the batch steps with a rule table (gol_batch_has_rules)."""
+        on = ctypes.c_uint32()
+        _check(lib().gol_batch_has_rules(self._h, ctypes.byref(on)))
+        return bool(on.value)
 
     def digest(self, first=0, count=None):
         """(live, hash): two uint64 arrays [count], per field what Engine.digest()

@@ -5,12 +5,14 @@
 // code that never touches the GPU; the host forms of load and store are the device
 // forms behind a compact staging buffer.  gol_batch_step_until_periodic drives
 // life_batch_until_kernel (life_batch_until.h) launch by launch, by the host-only plan
-// of gol_batch_until_plan_of.
+// of gol_batch_until_plan_of.  With a rule table (gol_batch_set_rules) both step by
+// life_batch_rules.h's kernels, which read every field's rule from the table.
 #include <cstdlib>
 
 #include "engine_internal.h"
 #include "life_batch.h"
 #include "life_batch_until.h"
+#include "life_batch_rules.h"
 
 struct gol_batch {
     int device = 0;
@@ -30,6 +32,9 @@ struct gol_batch {
     uint64_t* snap = nullptr;
     unsigned char* until = nullptr;
     gol::BatchUntilCounters counters = {};
+    // gol_batch_set_rules: field f's birth | survive << 16, [n] words; null = every field
+    // steps by the create rule
+    uint32_t* rules = nullptr;
 };
 
 namespace golh __attribute__((visibility("hidden"))) {
@@ -258,6 +263,7 @@ void gol_batch_destroy(gol_batch* b)
     if (b->stage) (void)hipFree(b->stage);
     if (b->snap) (void)hipFree(b->snap);
     if (b->until) (void)hipFree(b->until);
+    if (b->rules) (void)hipFree(b->rules);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -351,7 +357,11 @@ gol_status gol_batch_step(gol_batch* b, uint64_t generations)
     for (uint64_t left = generations; left > 0;) {
         const uint64_t g = std::min<uint64_t>(left, b->launch_gens);
         a.gens = (int32_t)g;
-        HIP_TRY(gol::launch_batch(a, (int)b->rows, b->rule, b->stream));
+        if (b->rules)
+            HIP_TRY(gol::launch_batch_rules(gol::BatchRuleArgs{a, b->rules}, (int)b->rows,
+                                            b->stream));
+        else
+            HIP_TRY(gol::launch_batch(a, (int)b->rows, b->rule, b->stream));
         left -= g;
     }
     return GOL_OK;
@@ -438,7 +448,11 @@ gol_status gol_batch_step_until_periodic(gol_batch* b, uint64_t max_generations,
         u.g0 = c0 * check_every;
         u.intervals = (uint32_t)std::min<uint64_t>(plan.checks_per_launch, plan.checks - c0);
         u.tail = j + 1 == plan.launches ? plan.tail : 0;
-        HIP_TRY(gol::launch_batch_until(u, (int)b->rows, b->rule, b->stream));
+        if (b->rules)
+            HIP_TRY(gol::launch_batch_until_rules(gol::BatchUntilRuleArgs{u, b->rules},
+                                                  (int)b->rows, b->stream));
+        else
+            HIP_TRY(gol::launch_batch_until(u, (int)b->rows, b->rule, b->stream));
         r.launches += 1;
         // a few bytes per launch: once no wavefront is pending, every field already holds
         // generation max_generations and nothing more is launched
@@ -462,6 +476,81 @@ gol_status gol_batch_step_until_periodic(gol_batch* b, uint64_t max_generations,
         if (generation) generation[i] = per[i] ? gen[i] : max_generations;
     }
     *out = r;
+    return GOL_OK;
+}
+
+gol_status gol_batch_set_rules(gol_batch* b, uint64_t first, uint64_t count,
+                               const uint32_t* birth, const uint32_t* survive)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (first > b->n || count > b->n - first)
+        return fail(GOL_EINVAL, "first + count exceeds the batch's fields");
+    if (count == 0) return GOL_OK;
+    if (!birth || !survive) return fail(GOL_EINVAL, "null birth or survive");
+    for (uint64_t i = 0; i < count; ++i)
+        if (birth[i] > 0x1FFu || survive[i] > 0x1FFu)
+            return fail(GOL_EINVAL, "rule masks are 9-bit");
+    HIP_TRY(hipSetDevice(b->device));
+    // the first table: every field's create rule around the caller's range, in one copy
+    const bool fresh = !b->rules;
+    const uint64_t lo = fresh ? 0 : first, words = fresh ? b->n : count;
+    std::vector<uint32_t> host(words, b->birth | b->survive << 16);
+    for (uint64_t i = 0; i < count; ++i) host[first - lo + i] = birth[i] | survive[i] << 16;
+    uint32_t* table = b->rules;
+    if (fresh && hipMalloc(&table, b->n * sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(GOL_ENOMEM, "the batch's rule table");
+    }
+    // on the batch's stream: behind the steps already enqueued
+    hipError_t e = hipMemcpyAsync(table + lo, host.data(), words * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) {
+        if (fresh) (void)hipFree(table);
+        HIP_TRY(e);
+    }
+    b->rules = table;
+    return GOL_OK;
+}
+
+gol_status gol_batch_get_rules(gol_batch* b, uint64_t first, uint64_t count, uint32_t* birth,
+                               uint32_t* survive)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (first > b->n || count > b->n - first)
+        return fail(GOL_EINVAL, "first + count exceeds the batch's fields");
+    if (count == 0) return GOL_OK;
+    std::vector<uint32_t> host(count, b->birth | b->survive << 16);
+    if (b->rules) {
+        HIP_TRY(hipSetDevice(b->device));
+        HIP_TRY(hipMemcpyAsync(host.data(), b->rules + first, count * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
+    for (uint64_t i = 0; i < count; ++i) {
+        if (birth) birth[i] = host[i] & 0xFFFFu;
+        if (survive) survive[i] = host[i] >> 16;
+    }
+    return GOL_OK;
+}
+
+gol_status gol_batch_drop_rules(gol_batch* b)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (!b->rules) return GOL_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    // (steps already enqueued still read the table)
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipFree(b->rules));
+    b->rules = nullptr;
+    return GOL_OK;
+}
+
+gol_status gol_batch_has_rules(gol_batch* b, uint32_t* on)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (!on) return fail(GOL_EINVAL, "null on");
+    *on = b->rules ? 1u : 0u;
     return GOL_OK;
 }
 

@@ -100,6 +100,7 @@ hipError_t launch_batch_digest(const BatchGeom& g, int64_t first, int64_t count,
 }  // namespace gol
 
 #ifdef GOL_BATCH_DEVICE
+#include "life_rule_lane.h"
 #include "life_stencil.h"
 
 namespace gol {
@@ -178,6 +179,7 @@ __device__ __forceinline__ Ends batch_ends(Pl<2>& x, const BatchLane& b)
 //   * a straight-line pass for h = R beside this one: 256 VGPRs and more, 1 wave per
 //     SIMD, with or without a scheduling fence between the steps;
 //   * groups of 8 steps under one test: 205 VGPRs and scratch.
+// birth, survive: the launch's masks (uniform), under RULE_LANE the lane's own.
 template <int R, int RULE, bool TORUS, bool MULTI>
 __device__ __forceinline__ void batch_pass(Pl<2> (&x)[R], Pl<2>& last, int32_t h,
                                            const BatchLane& b, uint32_t birth, uint32_t survive)
@@ -229,7 +231,11 @@ __device__ __forceinline__ void batch_pass(Pl<2> (&x)[R], Pl<2>& last, int32_t h
                 if (t == h) in = top;
             }
             const Ends e = batch_ends<TORUS, MULTI>(in, b);
-            Pl<2> y = stage_step_ends<RULE, 2>(st, in, e, birth, survive, (t & 1) == 1);
+            Pl<2> y;
+            if constexpr (RULE == RULE_LANE)
+                y = stage_step_lane<2>(st, in, e, birth, survive);
+            else
+                y = stage_step_ends<RULE, 2>(st, in, e, birth, survive, (t & 1) == 1);
             if constexpr (kMask) {
                 y.v[0] &= b.cm[0];
                 y.v[1] &= b.cm[1];
@@ -242,16 +248,34 @@ __device__ __forceinline__ void batch_pass(Pl<2> (&x)[R], Pl<2>& last, int32_t h
     }
 }
 
+// RULE_LANE: the masks a lane steps by, from the word of its field in the table
+// (birth | survive << 16), read once per launch.  All lanes of a field read the same
+// word; lanes without a word of a field < n (padding lanes, fields >= n) read nothing
+// and take the empty rule.
+struct LaneRule {
+    uint32_t birth, survive;
+};
+__device__ __forceinline__ LaneRule batch_lane_rule(const uint32_t* rules, int64_t f, bool live)
+{
+    uint32_t word = 0u;
+    if (live) word = rules[f];
+    return LaneRule{word & 0x1FFu, (word >> 16) & 0x1FFu};
+}
+
 // (life_batch_until.h's batch_until_run repeats the lane setup and the row load below
 // line for line, so that this kernel compiles as it did: change both together)
+// `rules`: RULE_LANE's table (life_batch_rules.h), unused by every other rule kind.
 template <int R, int RULE, bool TORUS, bool MULTI>
-__device__ __forceinline__ void batch_run(const BatchArgs& a, int64_t wave, int lane)
+__device__ __forceinline__ void batch_run(const BatchArgs& a, int64_t wave, int lane,
+                                          const uint32_t* rules = nullptr)
 {
     const int32_t h = a.h;
     const int lpf = 1 << a.lpf_shift;
     const int q = lane & (lpf - 1);
     const int64_t f = (wave << (6 - a.lpf_shift)) + (lane >> a.lpf_shift);
     const bool live = q < a.wq && f < a.n;
+    LaneRule rule = {};
+    if constexpr (RULE == RULE_LANE) rule = batch_lane_rule(rules, f, live);
     BatchLane b;
     const bool first = q == 0, last_lane = q == a.wq - 1;
     b.inner_l = first ? 0u : ~0u;
@@ -286,9 +310,13 @@ __device__ __forceinline__ void batch_run(const BatchArgs& a, int64_t wave, int 
         for (int r = 0; r < R; ++r)
             if (r == h - 1) last = x[r];
     }
+    // (the uniform kinds name a.birth and a.survive here and nowhere earlier: read into a
+    // local at the top, the 8- and 16-row kernels no longer compiled as they did)
 #pragma nounroll
     for (int32_t g = 0; g < a.gens; ++g)
-        batch_pass<R, RULE, TORUS, MULTI>(x, last, h, b, a.birth, a.survive);
+        batch_pass<R, RULE, TORUS, MULTI>(x, last, h, b,
+                                          RULE == RULE_LANE ? rule.birth : a.birth,
+                                          RULE == RULE_LANE ? rule.survive : a.survive);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (r < h) {

@@ -7,6 +7,7 @@
 #include "bitlayout.h"
 #include "life_batch.h"
 #include "life_batch_until.h"
+#include "life_batch_rules.h"
 
 namespace gol {
 
@@ -38,6 +39,38 @@ hipError_t launch_batch_until(const BatchUntilArgs& u, int rows, RuleKind rule, 
     case 16: return launch_batch_until_rows<16>(u, rule, s);
     case 32: return launch_batch_until_rows<32>(u, rule, s);
     case 64: return launch_batch_until_rows<64>(u, rule, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern template hipError_t launch_batch_rules_rows<8>(const BatchRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_rules_rows<16>(const BatchRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_rules_rows<32>(const BatchRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_rules_rows<64>(const BatchRuleArgs&, hipStream_t);
+
+hipError_t launch_batch_rules(const BatchRuleArgs& ra, int rows, hipStream_t s)
+{
+    switch (rows) {
+    case 8: return launch_batch_rules_rows<8>(ra, s);
+    case 16: return launch_batch_rules_rows<16>(ra, s);
+    case 32: return launch_batch_rules_rows<32>(ra, s);
+    case 64: return launch_batch_rules_rows<64>(ra, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern template hipError_t launch_batch_until_rules_rows<8>(const BatchUntilRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_until_rules_rows<16>(const BatchUntilRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_until_rules_rows<32>(const BatchUntilRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_until_rules_rows<64>(const BatchUntilRuleArgs&, hipStream_t);
+
+hipError_t launch_batch_until_rules(const BatchUntilRuleArgs& ru, int rows, hipStream_t s)
+{
+    switch (rows) {
+    case 8: return launch_batch_until_rules_rows<8>(ru, s);
+    case 16: return launch_batch_until_rules_rows<16>(ru, s);
+    case 32: return launch_batch_until_rules_rows<32>(ru, s);
+    case 64: return launch_batch_until_rules_rows<64>(ru, s);
     default: return hipErrorInvalidValue;
     }
 }

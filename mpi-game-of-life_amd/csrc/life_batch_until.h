@@ -112,7 +112,8 @@ __device__ __forceinline__ BatchUntilPlace batch_until_place(const BatchArgs& a,
 }
 
 template <int R, int RULE, bool TORUS, bool MULTI>
-__device__ __forceinline__ void batch_until_run(const BatchUntilArgs& u, int64_t wave, int lane)
+__device__ __forceinline__ void batch_until_run(const BatchUntilArgs& u, int64_t wave, int lane,
+                                                const uint32_t* rules = nullptr)
 {
     const BatchArgs& a = u.a;
     // (lane setup: batch_run's, line for line)
@@ -121,6 +122,8 @@ __device__ __forceinline__ void batch_until_run(const BatchUntilArgs& u, int64_t
     const int q = lane & (lpf - 1);
     const int64_t f = (wave << (6 - a.lpf_shift)) + (lane >> a.lpf_shift);
     const bool live = q < a.wq && f < a.n;
+    LaneRule rule = {};
+    if constexpr (RULE == RULE_LANE) rule = batch_lane_rule(rules, f, live);
     BatchLane b;
     const bool first = q == 0, last_lane = q == a.wq - 1;
     b.inner_l = first ? 0u : ~0u;
@@ -175,7 +178,9 @@ __device__ __forceinline__ void batch_until_run(const BatchUntilArgs& u, int64_t
     for (;;) {
 #pragma nounroll
         for (uint32_t i = 0; i < togo; ++i)
-            batch_pass<R, RULE, TORUS, MULTI>(x, last, h, b, a.birth, a.survive);
+            batch_pass<R, RULE, TORUS, MULTI>(x, last, h, b,
+                                              RULE == RULE_LANE ? rule.birth : a.birth,
+                                              RULE == RULE_LANE ? rule.survive : a.survive);
         computed += togo;
         if (phase == kEnd) break;
         const BatchUntilPlace p = batch_until_place(a, wave, lane);

@@ -22,7 +22,8 @@ namespace gol {
 enum RuleKind : int {
     RULE_REF = 0,     // birth = {}, survive = {2}: the reference's effective rule
     RULE_CONWAY = 1,  // birth = {3}, survive = {2,3}
-    RULE_GENERIC = 2  // any 9-bit mask pair, full 0..8 neighbour count
+    RULE_GENERIC = 2,  // any 9-bit mask pair, full 0..8 neighbour count
+    RULE_LANE = 3      // a mask pair per lane (batches with per-field rules, life_rule_lane.h)
 };
 
 // One independent field region streamed by the stencil kernel.
