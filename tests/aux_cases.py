@@ -1,7 +1,8 @@
 """The cases of tests/test_gpu_aux_scale.py, and why each is large enough.
 
 The auxiliary kernels (region I/O, density, ASCII codec, torus wrap in life_aux.hip,
-the snapshot compare in life_snap.hip) walk their work items with a grid-stride loop
+the snapshot compare in life_snap.hip, the batch codec in life_batch_aux.hip: cases 8 and
+9) walk their work items with a grid-stride loop
 over a capped grid: trip t of the loop handles the items [t C, (t + 1) C) with C the
 number of threads (or wavefronts) the capped grid holds.  A case belongs here if its
 item count is above C, so that the loop's increment runs, or if it stages more bytes
@@ -203,3 +204,40 @@ def composite_flips(h, w, row_starts, tile_rows=8, tile_words=64):
         for y, x in cells:
             out.append((leaf, snap_tile_of(y - r0, x, cdiv(w, 64), tile_rows, tile_words), (y, x)))
     return out
+
+
+# ---- the batch codec kernels (life_batch_aux.hip): items per launch
+
+def batch_codec_items(count, h, w):
+    """launch_batch_load / _store / _init_random: one thread per canonical word of the
+    fields of the call."""
+    return count * h * cdiv(w, 64)
+
+
+def batch_digest_items(count):
+    """launch_batch_digest: one wavefront per field."""
+    return count
+
+
+def batch_field_of_word(k, h, w):
+    """(field, row, word) of canonical word k of a batch."""
+    per = h * cdiv(w, 64)
+    return k // per, (k % per) // cdiv(w, 64), k % cdiv(w, 64)
+
+
+# Case 8: batch load, store and init_random.  4,100 x 64 x 9 = 2,361,600 words, 18.9 MB;
+# 9 words per row in 16 lanes per field, so 7 padding lanes per field and 4 fields per
+# wavefront.  Word 2,097,152, the second trip's first, is word 8 of row 56 of field 3,640.
+# `sub`: a store_packed(first, count) of one trip (1,100 x 576 = 633,600 words) that reads
+# fields on both sides of field 3,640; `sub_trip`: one of more than a trip's words
+# (3,700 x 576 = 2,131,200), which starts in its first trip and ends in its second.
+BATCH_CODEC = NS(n=4100, h=64, w=520, seed=61, gens=3, boundary=(3639, 3640, 3641),
+                 sub=(3000, 1100), sub_trip=(200, 3700), sampled_others=32)
+
+# Case 9: batch digest.  33,000 fields of 3 x 70 (2 words per row, 2 lanes per field),
+# one wavefront each: the fields from 32,768 on are the second trip's.
+BATCH_DIGEST = NS(n=33000, h=3, w=70, seed=62, sub=(32000, 1000))
+
+# The largest batch of the suite before these cases (test_gpu_batch_rules.py
+# test_every_rule_pair_once): exactly one trip of words.
+RULE_PAIRS = NS(n=262144, h=8, w=8)

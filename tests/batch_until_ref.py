@@ -16,10 +16,22 @@ def resolve(lag, check_every):
 
 def until_ref(cells, max_g, lag, check_every, rule, torus):
     """(period uint32 [n], generation uint64 [n], final uint8 [n, h, w] cells)."""
+    return _until(cells, max_g, lag, check_every, lambda a: batch_ref.run(a, 1, rule, torus))
+
+
+def until_ref_rules(cells, max_g, lag, check_every, birth, survive, torus):
+    """until_ref with a rule per field, (birth[i], survive[i]), over batch_rules_ref.run
+    (test_batch_lattice_host.py pins it to until_ref field by field)."""
+    import batch_rules_ref
+    return _until(cells, max_g, lag, check_every,
+                  lambda a: batch_rules_ref.run(a, 1, birth, survive, torus))
+
+
+def _until(cells, max_g, lag, check_every, step):
     C = resolve(lag, check_every)
     gens = [np.asarray(cells).astype(np.uint8)]
     for _ in range(max_g):
-        gens.append(batch_ref.run(gens[-1], 1, rule, torus))
+        gens.append(step(gens[-1]))
     n = gens[0].shape[0]
     period = np.zeros(n, dtype=np.uint32)
     generation = np.full(n, max_g, dtype=np.uint64)

@@ -256,3 +256,84 @@ def test_gpu_file_references():
     other = bytearray(text)
     other[777] ^= 1
     assert t.first_diff(bytes(other), text) == 777
+
+
+def batch_launcher_trips():
+    """launcher name -> items per trip of its kernel's loop in life_batch_aux.hip, as
+    launcher_trips() for life_aux.hip: batch_grid(items, per_block, cap)."""
+    src = source("life_batch_aux.hip")
+    assert re.search(r"dim3 batch_grid\(int64_t items, int64_t per_block, int64_t cap\)", src)
+    out = {}
+    bodies = re.split(r"\nhipError_t launch_batch_(\w+)\(", src)
+    for name, body in zip(bodies[1::2], bodies[2::2]):
+        m = re.search(r"batch_grid\((.*?),\s*(\d+),\s*(\d+)\)", body)
+        if not m:
+            continue
+        per_block, cap = int(m.group(2)), int(m.group(3))
+        assert per_block in (256, 256 // 64), (name, per_block)
+        assert "dim3(256)" in body, name
+        out[name] = (m.group(1).strip(), per_block * cap)
+    return out
+
+
+def test_batch_codec_patterns_match():
+    t = batch_launcher_trips()
+    assert set(t) >= {"load", "store", "init_random", "digest"}, sorted(t)
+    # the item counts the formulas of aux_cases.py restate
+    assert t["load"][0] == t["store"][0] == "count * g.h * g.wq"
+    assert t["init_random"][0] == "g.n * g.h * g.wq" and t["digest"][0] == "count"
+    for name in ("load", "store", "init_random", "digest"):
+        print(f"launch_batch_{name}: {t[name][1]} items per trip")
+    src = source("life_batch_aux.hip")
+    # the increments the second trips take: load, store, init_random; digest
+    assert len(re.findall(r"k \+= \(int64_t\)gridDim\.x \* blockDim\.x\)", src)) == 3
+    assert len(re.findall(r"for \(int64_t i = wave0; i < count; i \+= nwaves\)", src)) == 1
+    assert re.search(r"nwaves = \(\(int64_t\)gridDim\.x \* blockDim\.x\) >> 6;", src)
+
+
+def test_case8_batch_codec_items(pkg):
+    c, t = ac.BATCH_CODEC, batch_launcher_trips()
+    geo = pkg.batch_geometry(c.n, c.h, c.w)
+    assert (geo["lanes_per_field"], geo["fields_per_wave"]) == (16, 4)
+    assert geo["lanes_per_field"] > ac.cdiv(c.w, 64), "padding lanes"
+    items = ac.batch_codec_items(c.n, c.h, c.w)
+    for name in ("load", "store", "init_random"):
+        cap = t[name][1]
+        print(f"case 8 {name}: {items} / {cap}")
+        assert items > cap
+        f, r, q = ac.batch_field_of_word(cap, c.h, c.w)
+        print(f"case 8 {name}: the second trip starts at field {f}, row {r}, word {q}")
+        assert f == c.boundary[1] and 0 < r < c.h, "the trips' border lies inside a field"
+        assert c.boundary == (f - 1, f, f + 1) and f + 1 < c.n - 1
+    cap = t["store"][1]
+    first, count = c.sub
+    assert first < c.boundary[1] < first + count <= c.n
+    assert ac.batch_codec_items(count, c.h, c.w) <= cap
+    first, count = c.sub_trip
+    sub = ac.batch_codec_items(count, c.h, c.w)
+    print(f"case 8 sub-range store: {sub} / {cap}")
+    assert sub > cap and first > 0 and first + count < c.n
+    f, r, q = ac.batch_field_of_word(cap, c.h, c.w)
+    assert first + f < first + count
+
+
+def test_case9_batch_digest_items(pkg):
+    c, t = ac.BATCH_DIGEST, batch_launcher_trips()
+    cap = t["digest"][1]
+    items = ac.batch_digest_items(c.n)
+    print(f"case 9 digest: {items} / {cap}")
+    assert items > cap
+    first, count = c.sub
+    assert first < cap < first + count <= c.n, "the slice crosses the whole call's border"
+    assert ac.batch_digest_items(count) <= cap
+    assert pkg.batch_geometry(c.n, c.h, c.w)["lanes_per_field"] == 2
+
+
+def test_rule_pairs_batch_is_one_trip():
+    """Why the suite's largest batch before cases 8 and 9 was not enough: its words land
+    exactly on the cap, and digest was never called on it."""
+    c, t = ac.RULE_PAIRS, batch_launcher_trips()
+    items = ac.batch_codec_items(c.n, c.h, c.w)
+    for name in ("load", "store"):
+        print(f"test_every_rule_pair_once {name}: {items} / {t[name][1]}")
+        assert items <= t[name][1]

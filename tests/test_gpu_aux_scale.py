@@ -313,3 +313,80 @@ def test_composite_snapshot_second_trip(pkg, oracle):
         e.snapshot_restore()
         assert (e.store_packed() == a).all()
         assert e.snapshot_diff() == 0 and e.snapshot_same() is True
+
+
+def test_batch_codec_second_trip(pkg):
+    """Case 8: a batch of 2,361,600 words, 2,097,152 per trip of batch_load_kernel,
+    batch_store_kernel and batch_init_random_kernel; the trips' border lies in row 56 of
+    field 3,640."""
+    import batch_lattice as bl
+    import batch_ref
+
+    c = ac.BATCH_CODEC
+    n, h, w = c.n, c.h, c.w
+    wq = ac.cdiv(w, 64)
+    rng = np.random.default_rng(8)
+    with pkg.BatchEngine(n, h, w, rule=CONWAY, device=0) as b:
+        assert b.lanes_per_field == 16 and b.fields_per_wave == 4
+        # init_random: every field, against the synthetic field's numpy restatement
+        # (test_batch_lattice_host.py pins it to the oracle)
+        b.init_random(c.seed)
+        start = bl.synthetic_fields(0, n, h, w, c.seed)
+        got = b.store_packed()
+        bad = np.argwhere((got != start).any(axis=(1, 2))).ravel()
+        assert bad.size == 0, bad[:8].tolist()
+        # sub-range stores: one trip across field 3,640, and one of two trips of its own
+        for first, count in (c.sub, c.sub_trip):
+            part = b.store_packed(first, count)
+            bad = np.argwhere((part != start[first:first + count]).any(axis=(1, 2))).ravel()
+            assert bad.size == 0, (first, count, bad[:8].tolist())
+        # step: the sampled fields alone (the fields are independent)
+        sample = sorted({0, n - 1, *c.boundary,
+                         *rng.choice(n, c.sampled_others, replace=False).tolist()})
+        want = batch_ref.pack(batch_ref.run(batch_ref.unpack(start[sample], w), c.gens, CONWAY))
+        b.step(c.gens)
+        after = b.store_packed()
+        assert (after[sample] == want).all(), \
+            [sample[i] for i in np.argwhere((after[sample] != want).any(axis=(1, 2))).ravel()[:8]]
+        # load: all fields, junk at the columns >= w of every row's last word and in a
+        # spare word per row
+        words = rng.integers(0, 1 << 64, (n, h, wq + 1), dtype=np.uint64)
+        clean = words[:, :, :wq].copy()
+        clean[:, :, -1] &= bl.last_mask(w)
+        b.load_packed(words)
+        got = b.store_packed()
+        bad = np.argwhere((got != clean).any(axis=(1, 2))).ravel()
+        assert bad.size == 0, bad[:8].tolist()
+        # a sub-range load of two trips of its own, into the middle of the batch
+        first, count = c.sub_trip
+        b.load_packed(start[first:first + count], first=first)
+        clean[first:first + count] = start[first:first + count]
+        assert (b.store_packed() == clean).all()
+
+
+def test_batch_digest_second_trip(pkg):
+    """Case 9: 33,000 fields, 32,768 wavefronts per trip of batch_digest_kernel."""
+    import batch_lattice as bl
+
+    c = ac.BATCH_DIGEST
+    n, h, w = c.n, c.h, c.w
+    with pkg.BatchEngine(n, h, w, rule=CONWAY, device=0) as b:
+        b.init_random(c.seed)
+        fields = bl.synthetic_fields(0, n, h, w, c.seed)
+        assert (b.store_packed() == fields).all()
+        want_live, want_hash = bl.digests(fields)
+        live, hsh = b.digest()
+        bad = np.flatnonzero((live != want_live) | (hsh != want_hash))
+        assert bad.size == 0, bad[:8].tolist()
+        first, count = c.sub
+        live, hsh = b.digest(first, count)
+        assert live.tolist() == want_live[first:first + count].tolist()
+        assert hsh.tolist() == want_hash[first:first + count].tolist()
+        # after a step the digests follow the fields
+        import batch_ref
+        b.step(1)
+        live, hsh = b.digest()
+        after = batch_ref.pack(batch_ref.run(batch_ref.unpack(fields, w), 1, CONWAY))
+        assert (b.store_packed() == after).all()
+        want_live, want_hash = bl.digests(after)
+        assert live.tolist() == want_live.tolist() and hsh.tolist() == want_hash.tolist()
