@@ -677,6 +677,56 @@ typedef struct gol_batch_until_plan {
 gol_status gol_batch_until_plan_of(uint64_t max_generations, uint32_t lag, uint32_t check_every,
                                    uint32_t launch_generations, gol_batch_until_plan* out);
 
+/* Population traces: every field's live cells sampled in the kernel while it steps.
+ * With F_i(g) field i's state g generations after the call: live[s * sample_stride + i] =
+ * the live cells of F_i((s + 1) * every), for 0 <= s < samples = generations / every and
+ * 0 <= i < n; exactly the `live` gol_batch_digest would return at that generation.
+ * Elements at columns i >= n of a row of `live` are not touched.  On return every field
+ * holds F_i(generations), word for word what gol_batch_step(b, generations) leaves: the
+ * tail of generations % every generations is run and not sampled.  Each call counts from
+ * 0.  A count fits 32 bits (a field has at most 64 x 4096 cells).  While a rule table
+ * exists (gol_batch_set_rules) the call runs the rule-per-lane kernels, like
+ * gol_batch_step.  A sample costs one popcount per row and plane in the registers that
+ * hold the field between two generations, a sum over the field's lanes and one 4-byte
+ * store; the fields are loaded and stored once per launch, not once per sample.
+ * Both forms are synchronous like gol_batch_digest: they return after the caller's buffer
+ * is filled.  The _device form takes a device pointer on the batch's device; the host form
+ * is the device form behind a buffer of samples * n words that the batch owns, allocated
+ * at the first call, grown on demand (GOL_ENOMEM if that fails) and freed by
+ * gol_batch_destroy.
+ * Each launch covers whole sample intervals and the last one also runs the tail, as
+ * gol_batch_trace_plan_of tells; the call issues exactly that plan's launches.
+ * generations == 0: GOL_OK with nothing run.  generations < every: no samples, the fields
+ * stepped, one launch.
+ * GOL_EINVAL, before anything is stepped: null batch or out, out->struct_size not
+ * sizeof(gol_batch_trace), every == 0 or every > 65536 (gol_batch_step_until_periodic's
+ * bound on an interval, so that no launch outruns the launch cap by more than it does
+ * there), and while samples > 0: sample_stride < n, null live, samples * sample_stride
+ * not representable. */
+typedef struct gol_batch_trace {
+    uint32_t struct_size;   /* in: sizeof(gol_batch_trace), as gol_batch_until */
+    uint32_t every;         /* out: as used */
+    uint64_t samples;       /* out: generations / every */
+    uint32_t launches;      /* out: kernel launches issued by this call */
+    uint32_t reserved;
+} gol_batch_trace;
+gol_status gol_batch_step_trace(gol_batch* b, uint64_t generations, uint32_t every,
+                                uint32_t* live, uint64_t sample_stride, gol_batch_trace* out);
+gol_status gol_batch_step_trace_device(gol_batch* b, uint64_t generations, uint32_t every,
+                                       uint32_t* live, uint64_t sample_stride,
+                                       gol_batch_trace* out);
+
+/* Host-only, no GPU: how gol_batch_step_trace splits its work for a batch whose launch cap
+ * is launch_generations.  GOL_EINVAL: null out, every == 0, every > 65536. */
+typedef struct gol_batch_trace_plan {
+    uint64_t samples;             /* generations / every */
+    uint32_t tail;                /* generations % every */
+    uint32_t samples_per_launch;  /* max(1, launch_generations / every) */
+    uint64_t launches;            /* max(1, ceil(samples / samples_per_launch)) if generations > 0, else 0 */
+} gol_batch_trace_plan;
+gol_status gol_batch_trace_plan_of(uint64_t generations, uint32_t every,
+                                   uint32_t launch_generations, gol_batch_trace_plan* out);
+
 /* Per-field rules: one launch sweeps many rules.
  * gol_batch_set_rules gives field first + i the rule (birth[i], survive[i]), 9-bit masks
  * as gol_config's.  The first call with count > 0 allocates a device table of n words

@@ -52,6 +52,7 @@ EXPORTS = [
     "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step", "gol_batch_sync",
     "gol_batch_digest", "gol_batch_step_until_periodic", "gol_batch_until_plan_of",
     "gol_batch_set_rules", "gol_batch_get_rules", "gol_batch_drop_rules", "gol_batch_has_rules",
+    "gol_batch_step_trace", "gol_batch_step_trace_device", "gol_batch_trace_plan_of",
 ]
 
 # gol_step_until_periodic flag: run on to max_generations once a period is known
@@ -183,6 +184,30 @@ class BatchPeriods:
         return (f"BatchPeriods(found={self.found}/{len(self.period)}, lag={self.lag}, "
                 f"check_every={self.check_every}, launches={self.launches}, "
                 f"wave_generations={self.wave_generations})")
+
+
+class BatchTrace(ctypes.Structure):
+    """gol_batch_trace: the counters of gol_batch_step_trace."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),  # in: sizeof(gol_batch_trace) (gol.h)
+        ("every", ctypes.c_uint32),
+        ("samples", ctypes.c_uint64),
+        ("launches", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+    def __repr__(self):
+        return f"BatchTrace(every={self.every}, samples={self.samples}, launches={self.launches})"
+
+
+class BatchTracePlan(ctypes.Structure):
+    """gol_batch_trace_plan: how gol_batch_step_trace splits its work."""
+    _fields_ = [
+        ("samples", ctypes.c_uint64),
+        ("tail", ctypes.c_uint32),
+        ("samples_per_launch", ctypes.c_uint32),
+        ("launches", ctypes.c_uint64),
+    ]
 
 
 class SchedOp(ctypes.Structure):
@@ -328,12 +353,16 @@ def lib():
     L.gol_batch_get_rules.argtypes = [vp, u64, u64, vp, vp]
     L.gol_batch_drop_rules.argtypes = [vp]
     L.gol_batch_has_rules.argtypes = [vp, pu32]
+    L.gol_batch_step_trace.argtypes = [vp, u64, u32, vp, u64, ctypes.POINTER(BatchTrace)]
+    L.gol_batch_step_trace_device.argtypes = [vp, u64, u32, vp, u64, ctypes.POINTER(BatchTrace)]
+    L.gol_batch_trace_plan_of.argtypes = [u64, u32, u32, ctypes.POINTER(BatchTracePlan)]
     for name in ["gol_batch_geometry", "gol_batch_create", "gol_batch_info",
                  "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
                  "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step",
                  "gol_batch_sync", "gol_batch_digest", "gol_batch_step_until_periodic",
                  "gol_batch_until_plan_of", "gol_batch_set_rules", "gol_batch_get_rules",
-                 "gol_batch_drop_rules", "gol_batch_has_rules"]:
+                 "gol_batch_drop_rules", "gol_batch_has_rules", "gol_batch_step_trace",
+                 "gol_batch_step_trace_device", "gol_batch_trace_plan_of"]:
         getattr(L, name).restype = ctypes.c_int
     for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit", "gol_snapshot",
                  "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
@@ -537,6 +566,16 @@ def batch_until_plan(max_generations, lag, check_every=0, launch_generations=409
                                          ctypes.byref(p)))
     return {"check_every": p.check_every, "divisors": list(p.divisors[:p.ndivisors]),
             "checks": p.checks, "tail": p.tail, "checks_per_launch": p.checks_per_launch,
+            "launches": p.launches}
+
+
+def batch_trace_plan(generations, every, launch_generations=4096):
+    """gol_batch_trace_plan_of (host only, no GPU): how BatchEngine.step_trace splits its
+    work on a batch whose launch cap is launch_generations.  Returns a dict: samples, tail,
+    samples_per_launch, launches."""
+    p = BatchTracePlan()
+    _check(lib().gol_batch_trace_plan_of(generations, every, launch_generations, ctypes.byref(p)))
+    return {"samples": p.samples, "tail": p.tail, "samples_per_launch": p.samples_per_launch,
             "launches": p.launches}
 
 
@@ -872,6 +911,7 @@ class BatchEngine:
         self.n, self.h, self.w, self.device = n, h, w, device
         self.wq = (w + 63) // 64
         self._h = None
+        self.last_trace = None
         cfg = make_config(rule, device, semantics)
         handle = ctypes.c_void_p()
         _check(lib().gol_batch_create(n, h, w, ctypes.byref(cfg), ctypes.byref(handle)))
@@ -983,6 +1023,47 @@ class BatchEngine:
                                                    period.ctypes.data, generation.ctypes.data,
                                                    ctypes.byref(r)))
         return BatchPeriods(period, generation, r)
+
+    def _trace_samples(self, generations, every):
+        # (the shape of the result; the call itself rejects a bad `every`)
+        import operator
+        try:
+            every = operator.index(every)
+        except TypeError:
+            every = 0
+        if every < 1 or every > 65536:
+            raise GolError(GOL_EINVAL, "a batch trace's `every` must be 1..65536")
+        return generations // every
+
+    def step_trace(self, generations, every=1):
+        """Steps every field `generations` generations and samples its live cells every
+        `every` of them, in the kernel (gol_batch_step_trace).  Returns a uint32 array
+        [generations // every, n]: row s holds the counts (s + 1) * every generations after
+        the call, what digest()[0] would return there.  On return every field holds what
+        step(generations) would have left.  The call's counters (every, samples, launches)
+        are in last_trace, a BatchTrace."""
+        import numpy as np
+        live = np.zeros((self._trace_samples(generations, every), self.n), dtype=np.uint32)
+        r = BatchTrace(struct_size=ctypes.sizeof(BatchTrace))
+        _check(lib().gol_batch_step_trace(self._h, generations, every, live.ctypes.data, self.n,
+                                          ctypes.byref(r)))
+        self.last_trace = r
+        return live
+
+    def step_trace_tensor(self, generations, every=1):
+        """step_trace into a new contiguous torch.int32 CUDA tensor [generations // every, n]
+        on the batch's device (gol_batch_step_trace_device: no sample crosses to the host;
+        with device=-1 at create that is taken to be torch's current device)."""
+        import torch
+        dev = torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
+        t = torch.zeros((self._trace_samples(generations, every), self.n), dtype=torch.int32,
+                        device=dev)
+        torch.cuda.current_stream(t.device).synchronize()
+        r = BatchTrace(struct_size=ctypes.sizeof(BatchTrace))
+        _check(lib().gol_batch_step_trace_device(self._h, generations, every, t.data_ptr(),
+                                                 self.n, ctypes.byref(r)))
+        self.last_trace = r
+        return t
 
     def set_rules(self, birth, survive, first=0):
         """Fields [first, first + len(birth)) get the rules (birth[i], survive[i]), 9-bit

@@ -7,12 +7,15 @@
 // life_batch_until_kernel (life_batch_until.h) launch by launch, by the host-only plan
 // of gol_batch_until_plan_of.  With a rule table (gol_batch_set_rules) both step by
 // life_batch_rules.h's kernels, which read every field's rule from the table.
+// gol_batch_step_trace drives life_batch_trace_kernel (life_batch_trace.h) by the host-only
+// plan of gol_batch_trace_plan_of.
 #include <cstdlib>
 
 #include "engine_internal.h"
 #include "life_batch.h"
 #include "life_batch_until.h"
 #include "life_batch_rules.h"
+#include "life_batch_trace.h"
 
 struct gol_batch {
     int device = 0;
@@ -35,6 +38,10 @@ struct gol_batch {
     // gol_batch_set_rules: field f's birth | survive << 16, [n] words; null = every field
     // steps by the create rule
     uint32_t* rules = nullptr;
+    // gol_batch_step_trace's host form: the samples on the device ([samples][n] words),
+    // allocated by its first call and grown on demand
+    uint32_t* trace = nullptr;
+    size_t trace_words = 0;
 };
 
 namespace golh __attribute__((visibility("hidden"))) {
@@ -180,6 +187,68 @@ gol_status until_args(uint32_t lag, uint32_t* check_every)
     return GOL_OK;
 }
 
+// The checks gol_batch_step_trace, its device form and gol_batch_trace_plan_of share.
+gol_status trace_every(uint32_t every)
+{
+    if (every == 0 || every > gol::kBatchTraceMaxEvery)
+        return fail(GOL_EINVAL, "a batch trace's `every` must be 1..65536");
+    return GOL_OK;
+}
+
+// Every GOL_EINVAL of gol_batch_step_trace and its device form, in the header's order;
+// *plan: the call's launches.
+gol_status trace_check(const gol_batch* b, uint64_t generations, uint32_t every,
+                       const uint32_t* live, uint64_t stride, const gol_batch_trace* out,
+                       gol_batch_trace_plan* plan)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (!out) return fail(GOL_EINVAL, "null out");
+    if (out->struct_size != sizeof(gol_batch_trace))
+        return fail(GOL_EINVAL, "gol_batch_trace.struct_size must be sizeof(gol_batch_trace)");
+    GOL_TRY(trace_every(every));
+    GOL_TRY(gol_batch_trace_plan_of(generations, every, b->launch_gens, plan));
+    if (plan->samples > 0) {
+        if (stride < b->n) return fail(GOL_EINVAL, "sample_stride < n");
+        if (!live) return fail(GOL_EINVAL, "null live");
+        // (in bytes too: the words are addressed in a buffer)
+        if (stride > (UINT64_MAX / sizeof(uint32_t)) / plan->samples)
+            return fail(GOL_EINVAL, "samples * sample_stride is not representable");
+    }
+    return GOL_OK;
+}
+
+// The plan's launches, samples to dev[s * stride + i]; waits for them.
+gol_status trace_run(gol_batch* b, const gol_batch_trace_plan& plan, uint32_t every,
+                     uint32_t* dev, uint64_t stride, gol_batch_trace* out)
+{
+    gol_batch_trace r = {};
+    r.struct_size = sizeof(gol_batch_trace);
+    r.every = every;
+    r.samples = plan.samples;
+    if (plan.launches > 0) {
+        gol::BatchTraceArgs t{};
+        t.a = args_of(b);
+        t.trace = dev;
+        t.stride = stride;
+        t.every = every;
+        for (uint64_t j = 0; j < plan.launches; ++j) {
+            t.s0 = j * plan.samples_per_launch;
+            t.intervals =
+                (uint32_t)std::min<uint64_t>(plan.samples_per_launch, plan.samples - t.s0);
+            t.tail = j + 1 == plan.launches ? plan.tail : 0;
+            if (b->rules)
+                HIP_TRY(gol::launch_batch_trace_rules(gol::BatchTraceRuleArgs{t, b->rules},
+                                                      (int)b->rows, b->stream));
+            else
+                HIP_TRY(gol::launch_batch_trace(t, (int)b->rows, b->rule, b->stream));
+            r.launches += 1;
+        }
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
+    *out = r;
+    return GOL_OK;
+}
+
 }  // namespace
 
 }  // namespace golh
@@ -264,6 +333,7 @@ void gol_batch_destroy(gol_batch* b)
     if (b->snap) (void)hipFree(b->snap);
     if (b->until) (void)hipFree(b->until);
     if (b->rules) (void)hipFree(b->rules);
+    if (b->trace) (void)hipFree(b->trace);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -476,6 +546,66 @@ gol_status gol_batch_step_until_periodic(gol_batch* b, uint64_t max_generations,
         if (generation) generation[i] = per[i] ? gen[i] : max_generations;
     }
     *out = r;
+    return GOL_OK;
+}
+
+gol_status gol_batch_trace_plan_of(uint64_t generations, uint32_t every,
+                                   uint32_t launch_generations, gol_batch_trace_plan* out)
+{
+    if (!out) return fail(GOL_EINVAL, "null out");
+    GOL_TRY(trace_every(every));
+    gol_batch_trace_plan p = {};
+    p.samples = generations / every;
+    p.tail = (uint32_t)(generations % every);
+    p.samples_per_launch = std::max<uint32_t>(1, launch_generations / every);
+    p.launches = (p.samples + p.samples_per_launch - 1) / p.samples_per_launch;
+    if (p.launches == 0 && generations > 0) p.launches = 1;
+    *out = p;
+    return GOL_OK;
+}
+
+gol_status gol_batch_step_trace_device(gol_batch* b, uint64_t generations, uint32_t every,
+                                       uint32_t* live, uint64_t sample_stride,
+                                       gol_batch_trace* out)
+{
+    gol_batch_trace_plan plan;
+    GOL_TRY(trace_check(b, generations, every, live, sample_stride, out, &plan));
+    HIP_TRY(hipSetDevice(b->device));
+    return trace_run(b, plan, every, live, sample_stride, out);
+}
+
+gol_status gol_batch_step_trace(gol_batch* b, uint64_t generations, uint32_t every,
+                                uint32_t* live, uint64_t sample_stride, gol_batch_trace* out)
+{
+    gol_batch_trace_plan plan;
+    GOL_TRY(trace_check(b, generations, every, live, sample_stride, out, &plan));
+    HIP_TRY(hipSetDevice(b->device));
+    // (samples * n <= samples * sample_stride, which trace_check has bounded)
+    const size_t words = (size_t)(plan.samples * b->n);
+    if (b->trace_words < words) {
+        if (b->trace) {
+            HIP_TRY(hipStreamSynchronize(b->stream));
+            (void)hipFree(b->trace);
+            b->trace = nullptr;
+            b->trace_words = 0;
+        }
+        if (hipMalloc(&b->trace, words * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            b->trace = nullptr;
+            return fail(GOL_ENOMEM, "the batch's trace buffer");
+        }
+        b->trace_words = words;
+    }
+    GOL_TRY(trace_run(b, plan, every, b->trace, b->n, out));
+    if (words == 0) return GOL_OK;
+    const size_t rowb = b->n * sizeof(uint32_t);
+    if (sample_stride == b->n)
+        HIP_TRY(hipMemcpyAsync(live, b->trace, words * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               b->stream));
+    else
+        HIP_TRY(hipMemcpy2DAsync(live, sample_stride * sizeof(uint32_t), b->trace, rowb, rowb,
+                                 plan.samples, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
     return GOL_OK;
 }
 

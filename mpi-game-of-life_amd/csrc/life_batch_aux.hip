@@ -8,6 +8,7 @@
 #include "life_batch.h"
 #include "life_batch_until.h"
 #include "life_batch_rules.h"
+#include "life_batch_trace.h"
 
 namespace gol {
 
@@ -71,6 +72,38 @@ hipError_t launch_batch_until_rules(const BatchUntilRuleArgs& ru, int rows, hipS
     case 16: return launch_batch_until_rules_rows<16>(ru, s);
     case 32: return launch_batch_until_rules_rows<32>(ru, s);
     case 64: return launch_batch_until_rules_rows<64>(ru, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern template hipError_t launch_batch_trace_rows<8>(const BatchTraceArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_trace_rows<16>(const BatchTraceArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_trace_rows<32>(const BatchTraceArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_trace_rows<64>(const BatchTraceArgs&, RuleKind, hipStream_t);
+
+hipError_t launch_batch_trace(const BatchTraceArgs& t, int rows, RuleKind rule, hipStream_t s)
+{
+    switch (rows) {
+    case 8: return launch_batch_trace_rows<8>(t, rule, s);
+    case 16: return launch_batch_trace_rows<16>(t, rule, s);
+    case 32: return launch_batch_trace_rows<32>(t, rule, s);
+    case 64: return launch_batch_trace_rows<64>(t, rule, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern template hipError_t launch_batch_trace_rules_rows<8>(const BatchTraceRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_trace_rules_rows<16>(const BatchTraceRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_trace_rules_rows<32>(const BatchTraceRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_trace_rules_rows<64>(const BatchTraceRuleArgs&, hipStream_t);
+
+hipError_t launch_batch_trace_rules(const BatchTraceRuleArgs& rt, int rows, hipStream_t s)
+{
+    switch (rows) {
+    case 8: return launch_batch_trace_rules_rows<8>(rt, s);
+    case 16: return launch_batch_trace_rules_rows<16>(rt, s);
+    case 32: return launch_batch_trace_rules_rows<32>(rt, s);
+    case 64: return launch_batch_trace_rules_rows<64>(rt, s);
     default: return hipErrorInvalidValue;
     }
 }
