@@ -727,6 +727,54 @@ typedef struct gol_batch_trace_plan {
 gol_status gol_batch_trace_plan_of(uint64_t generations, uint32_t every,
                                    uint32_t launch_generations, gol_batch_trace_plan* out);
 
+/* Rollouts: the states of a window of fields, written by the kernel while it steps.
+ * With F_i(g) field i's state g generations after the call, for 0 <= s < samples =
+ * generations / every, 0 <= j < count, r < h and q < ceil(w/64):
+ *   frames[s * sample_stride_words + j * field_stride_words + r * row_stride_words + q]
+ *       = canonical word q of row r of F_{first+j}((s + 1) * every),
+ * exactly the words gol_batch_store_packed(b, first, count, ...) would write at that
+ * generation; bits at columns >= w are 0.  No other word of `frames` is touched: gaps left
+ * by wider strides keep what they held.  On return every one of the n fields, inside the
+ * window or not, holds F_i(generations), word for word what gol_batch_step(b, generations)
+ * leaves: the tail of generations % every generations is run and not recorded.  Each call
+ * counts from 0.  While a rule table exists (gol_batch_set_rules) the call runs the
+ * rule-per-lane kernels, like gol_batch_step.  A sample costs one 8-byte store per row by
+ * every lane that holds a word of a field of the window, from the registers that hold the
+ * field between two generations; wavefronts with no field in the window store nothing, and
+ * the fields are loaded and stored once per launch, not once per sample.
+ * Both forms are synchronous like gol_batch_step_trace: they return after the caller's
+ * buffer is filled.  The _device form takes a device pointer on the batch's device; the
+ * host form is the device form behind a compact buffer of samples * count * h * ceil(w/64)
+ * words that the batch owns, allocated at the first call, grown on demand (GOL_ENOMEM if
+ * that fails, and the fields are not stepped) and freed by gol_batch_destroy, which is then
+ * copied to the caller with the caller's strides.
+ * The call issues exactly the launches of gol_batch_trace_plan_of(generations, every,
+ * launch_generations): whole sample intervals per launch, the tail in the last one.
+ * generations == 0: GOL_OK with nothing run.  generations < every: no samples, the fields
+ * stepped, one launch.  count == 0: the fields are stepped and nothing is recorded.
+ * GOL_EINVAL, before anything is stepped and with nothing changed, in this order: null
+ * batch; null out; out->struct_size not sizeof(gol_batch_record); every == 0 or
+ * every > 65536; first + count > n; and while samples > 0 and count > 0:
+ * row_stride_words < ceil(w/64), field_stride_words < h * row_stride_words,
+ * sample_stride_words < count * field_stride_words, null frames,
+ * samples * sample_stride_words * 8 not representable. */
+typedef struct gol_batch_record {
+    uint32_t struct_size;   /* in: sizeof(gol_batch_record), as gol_batch_trace */
+    uint32_t every;         /* out: as used */
+    uint64_t samples;       /* out: generations / every */
+    uint32_t launches;      /* out: kernel launches issued by this call */
+    uint32_t reserved;
+} gol_batch_record;
+gol_status gol_batch_step_record(gol_batch* b, uint64_t generations, uint32_t every,
+                                 uint64_t first, uint64_t count, uint64_t* frames,
+                                 uint64_t sample_stride_words, uint64_t field_stride_words,
+                                 uint64_t row_stride_words, gol_batch_record* out);
+gol_status gol_batch_step_record_device(gol_batch* b, uint64_t generations, uint32_t every,
+                                        uint64_t first, uint64_t count, uint64_t* frames,
+                                        uint64_t sample_stride_words,
+                                        uint64_t field_stride_words, uint64_t row_stride_words,
+                                        gol_batch_record* out);
+
 /* Per-field rules: one launch sweeps many rules.
  * gol_batch_set_rules gives field first + i the rule (birth[i], survive[i]), 9-bit masks
  * as gol_config's.  The first call with count > 0 allocates a device table of n words

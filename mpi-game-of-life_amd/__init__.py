@@ -53,6 +53,7 @@ EXPORTS = [
     "gol_batch_digest", "gol_batch_step_until_periodic", "gol_batch_until_plan_of",
     "gol_batch_set_rules", "gol_batch_get_rules", "gol_batch_drop_rules", "gol_batch_has_rules",
     "gol_batch_step_trace", "gol_batch_step_trace_device", "gol_batch_trace_plan_of",
+    "gol_batch_step_record", "gol_batch_step_record_device",
 ]
 
 # gol_step_until_periodic flag: run on to max_generations once a period is known
@@ -210,6 +211,20 @@ class BatchTracePlan(ctypes.Structure):
     ]
 
 
+class BatchRecord(ctypes.Structure):
+    """gol_batch_record: the counters of gol_batch_step_record."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),  # in: sizeof(gol_batch_record) (gol.h)
+        ("every", ctypes.c_uint32),
+        ("samples", ctypes.c_uint64),
+        ("launches", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+    def __repr__(self):
+        return f"BatchRecord(every={self.every}, samples={self.samples}, launches={self.launches})"
+
+
 class SchedOp(ctypes.Structure):
     _fields_ = [
         ("kind", ctypes.c_uint32),
@@ -356,13 +371,17 @@ def lib():
     L.gol_batch_step_trace.argtypes = [vp, u64, u32, vp, u64, ctypes.POINTER(BatchTrace)]
     L.gol_batch_step_trace_device.argtypes = [vp, u64, u32, vp, u64, ctypes.POINTER(BatchTrace)]
     L.gol_batch_trace_plan_of.argtypes = [u64, u32, u32, ctypes.POINTER(BatchTracePlan)]
+    for name in ["gol_batch_step_record", "gol_batch_step_record_device"]:
+        getattr(L, name).argtypes = [vp, u64, u32, u64, u64, vp, u64, u64, u64,
+                                     ctypes.POINTER(BatchRecord)]
     for name in ["gol_batch_geometry", "gol_batch_create", "gol_batch_info",
                  "gol_batch_load_packed", "gol_batch_store_packed", "gol_batch_load_device",
                  "gol_batch_store_device", "gol_batch_init_random", "gol_batch_step",
                  "gol_batch_sync", "gol_batch_digest", "gol_batch_step_until_periodic",
                  "gol_batch_until_plan_of", "gol_batch_set_rules", "gol_batch_get_rules",
                  "gol_batch_drop_rules", "gol_batch_has_rules", "gol_batch_step_trace",
-                 "gol_batch_step_trace_device", "gol_batch_trace_plan_of"]:
+                 "gol_batch_step_trace_device", "gol_batch_trace_plan_of",
+                 "gol_batch_step_record", "gol_batch_step_record_device"]:
         getattr(L, name).restype = ctypes.c_int
     for name in ["gol_read_rect", "gol_write_rect", "gol_density", "gol_rect_blit", "gol_snapshot",
                  "gol_snapshot_same", "gol_snapshot_diff", "gol_snapshot_restore",
@@ -577,6 +596,33 @@ def batch_trace_plan(generations, every, launch_generations=4096):
     _check(lib().gol_batch_trace_plan_of(generations, every, launch_generations, ctypes.byref(p)))
     return {"samples": p.samples, "tail": p.tail, "samples_per_launch": p.samples_per_launch,
             "launches": p.launches}
+
+
+def unpack_cells(words, w):
+    """Packed frames to cells: uint64 [..., h, >= ceil(w/64)] canonical words (what
+    BatchEngine.step_record and store_packed return) -> uint8 [..., h, w]."""
+    import numpy as np
+    a = np.ascontiguousarray(words, dtype=np.uint64)
+    if a.ndim < 2 or w < 1 or a.shape[-1] * 64 < w:
+        raise GolError(GOL_EINVAL, "words must be a uint64 array [..., h, >= ceil(w/64)]")
+    bits = np.unpackbits(a.view(np.uint8).reshape(a.shape[:-1] + (-1,)), axis=-1,
+                         bitorder="little")
+    return np.ascontiguousarray(bits[..., :w])
+
+
+def pack_cells(cells):
+    """The inverse of unpack_cells: [..., h, w] cells (nonzero = live) -> uint64
+    [..., h, ceil(w/64)] canonical words, zero-padded to whole words."""
+    import numpy as np
+    c = np.asarray(cells)
+    if c.ndim < 2 or c.shape[-1] < 1:
+        raise GolError(GOL_EINVAL, "cells must be an array [..., h, w] with w >= 1")
+    w = c.shape[-1]
+    wq = (w + 63) // 64
+    b = np.zeros(c.shape[:-1] + (wq * 64,), dtype=np.uint8)
+    b[..., :w] = c != 0
+    packed = np.packbits(b, axis=-1, bitorder="little")
+    return np.ascontiguousarray(packed).view(np.uint64).reshape(c.shape[:-1] + (wq,))
 
 
 def unique_id() -> bytes:
@@ -912,6 +958,7 @@ class BatchEngine:
         self.wq = (w + 63) // 64
         self._h = None
         self.last_trace = None
+        self.last_record = None
         cfg = make_config(rule, device, semantics)
         handle = ctypes.c_void_p()
         _check(lib().gol_batch_create(n, h, w, ctypes.byref(cfg), ctypes.byref(handle)))
@@ -1063,6 +1110,57 @@ class BatchEngine:
         _check(lib().gol_batch_step_trace_device(self._h, generations, every, t.data_ptr(),
                                                  self.n, ctypes.byref(r)))
         self.last_trace = r
+        return t
+
+    def _record_shape(self, generations, every, first, count):
+        # (the shape of the result; the call itself rejects a bad `every` or window)
+        import operator
+        try:
+            every, first = operator.index(every), operator.index(first)
+            count = self.n - first if count is None else operator.index(count)
+        except TypeError:
+            raise GolError(GOL_EINVAL, "a batch record's every, first and count are integers")
+        if every < 1 or every > 65536:
+            raise GolError(GOL_EINVAL, "a batch record's `every` must be 1..65536")
+        if first < 0 or count < 0 or first + count > self.n:
+            raise GolError(GOL_EINVAL, "first + count exceeds the batch's fields")
+        return (generations // every, count, self.h, self.wq), first, count
+
+    def step_record(self, generations, every=1, first=0, count=None):
+        """Steps every field `generations` generations and records the states of fields
+        [first, first + count) every `every` of them, written by the kernel
+        (gol_batch_step_record).  Returns a uint64 array [generations // every, count, h,
+        ceil(w/64)]: frame s holds what store_packed(first, count) would return (s + 1) *
+        every generations after the call (unpack_cells turns frames into cells).  On return
+        every field, in the window or not, holds what step(generations) would have left.
+        The call's counters (every, samples, launches) are in last_record, a BatchRecord."""
+        import numpy as np
+        shape, first, count = self._record_shape(generations, every, first, count)
+        frames = np.zeros(shape, dtype=np.uint64)
+        fs = self.h * self.wq
+        r = BatchRecord(struct_size=ctypes.sizeof(BatchRecord))
+        _check(lib().gol_batch_step_record(self._h, generations, every, first, count,
+                                           frames.ctypes.data, count * fs, fs, self.wq,
+                                           ctypes.byref(r)))
+        self.last_record = r
+        return frames
+
+    def step_record_tensor(self, generations, every=1, first=0, count=None):
+        """step_record into a new contiguous torch.int64 CUDA tensor [generations // every,
+        count, h, ceil(w/64)] on the batch's device (gol_batch_step_record_device: no frame
+        crosses to the host; with device=-1 at create that is taken to be torch's current
+        device)."""
+        import torch
+        shape, first, count = self._record_shape(generations, every, first, count)
+        dev = torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
+        t = torch.zeros(shape, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(t.device).synchronize()
+        fs = self.h * self.wq
+        r = BatchRecord(struct_size=ctypes.sizeof(BatchRecord))
+        _check(lib().gol_batch_step_record_device(self._h, generations, every, first, count,
+                                                  t.data_ptr(), count * fs, fs, self.wq,
+                                                  ctypes.byref(r)))
+        self.last_record = r
         return t
 
     def set_rules(self, birth, survive, first=0):

@@ -8,14 +8,18 @@
 // of gol_batch_until_plan_of.  With a rule table (gol_batch_set_rules) both step by
 // life_batch_rules.h's kernels, which read every field's rule from the table.
 // gol_batch_step_trace drives life_batch_trace_kernel (life_batch_trace.h) by the host-only
-// plan of gol_batch_trace_plan_of.
+// plan of gol_batch_trace_plan_of; gol_batch_step_record drives life_batch_record_kernel
+// (life_batch_record.h) by the same plan.
 #include <cstdlib>
+#include <cstring>
+#include <new>
 
 #include "engine_internal.h"
 #include "life_batch.h"
 #include "life_batch_until.h"
 #include "life_batch_rules.h"
 #include "life_batch_trace.h"
+#include "life_batch_record.h"
 
 struct gol_batch {
     int device = 0;
@@ -42,6 +46,10 @@ struct gol_batch {
     // allocated by its first call and grown on demand
     uint32_t* trace = nullptr;
     size_t trace_words = 0;
+    // gol_batch_step_record's host form: the frames on the device, compact
+    // ([samples][count][h][wq] words), allocated by its first call and grown on demand
+    uint64_t* record = nullptr;
+    size_t record_words = 0;
 };
 
 namespace golh __attribute__((visibility("hidden"))) {
@@ -249,6 +257,74 @@ gol_status trace_run(gol_batch* b, const gol_batch_trace_plan& plan, uint32_t ev
     return GOL_OK;
 }
 
+// Every GOL_EINVAL of gol_batch_step_record and its device form, in the header's order;
+// *plan: the call's launches (gol_batch_trace_plan_of's: there is no second plan).
+gol_status record_check(const gol_batch* b, uint64_t generations, uint32_t every, uint64_t first,
+                        uint64_t count, const uint64_t* frames, uint64_t ss, uint64_t fs,
+                        uint64_t rs, const gol_batch_record* out, gol_batch_trace_plan* plan)
+{
+    if (!b) return fail(GOL_EINVAL, "null batch");
+    if (!out) return fail(GOL_EINVAL, "null out");
+    if (out->struct_size != sizeof(gol_batch_record))
+        return fail(GOL_EINVAL, "gol_batch_record.struct_size must be sizeof(gol_batch_record)");
+    if (every == 0 || every > gol::kBatchRecordMaxEvery)
+        return fail(GOL_EINVAL, "a batch record's `every` must be 1..65536");
+    if (first > b->n || count > b->n - first)
+        return fail(GOL_EINVAL, "first + count exceeds the batch's fields");
+    GOL_TRY(gol_batch_trace_plan_of(generations, every, b->launch_gens, plan));
+    if (plan->samples > 0 && count > 0) {
+        // (a product that does not fit 64 bits is above every stride)
+        if (rs < b->wq) return fail(GOL_EINVAL, "row_stride_words < ceil(w/64)");
+        if (rs > UINT64_MAX / b->h || fs < b->h * rs)
+            return fail(GOL_EINVAL, "field_stride_words < h * row_stride_words");
+        if (fs > UINT64_MAX / count || ss < count * fs)
+            return fail(GOL_EINVAL, "sample_stride_words < count * field_stride_words");
+        if (!frames) return fail(GOL_EINVAL, "null frames");
+        // (in bytes: the words are addressed in a buffer)
+        if (ss > (UINT64_MAX / sizeof(uint64_t)) / plan->samples)
+            return fail(GOL_EINVAL, "samples * sample_stride_words is not representable");
+    }
+    return GOL_OK;
+}
+
+// The plan's launches, sample s of field first + j to dev[s * ss + j * fs + r * rs + q];
+// waits for them.
+gol_status record_run(gol_batch* b, const gol_batch_trace_plan& plan, uint32_t every,
+                      uint64_t first, uint64_t count, uint64_t* dev, uint64_t ss, uint64_t fs,
+                      uint64_t rs, gol_batch_record* out)
+{
+    gol_batch_record r = {};
+    r.struct_size = sizeof(gol_batch_record);
+    r.every = every;
+    r.samples = plan.samples;
+    if (plan.launches > 0) {
+        gol::BatchRecordArgs t{};
+        t.a = args_of(b);
+        t.frames = dev;
+        t.ss = ss;
+        t.fs = fs;
+        t.rs = rs;
+        t.first = (int64_t)first;
+        t.count = (int64_t)count;
+        t.every = every;
+        for (uint64_t j = 0; j < plan.launches; ++j) {
+            t.s0 = j * plan.samples_per_launch;
+            t.intervals =
+                (uint32_t)std::min<uint64_t>(plan.samples_per_launch, plan.samples - t.s0);
+            t.tail = j + 1 == plan.launches ? plan.tail : 0;
+            if (b->rules)
+                HIP_TRY(gol::launch_batch_record_rules(gol::BatchRecordRuleArgs{t, b->rules},
+                                                       (int)b->rows, b->stream));
+            else
+                HIP_TRY(gol::launch_batch_record(t, (int)b->rows, b->rule, b->stream));
+            r.launches += 1;
+        }
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
+    *out = r;
+    return GOL_OK;
+}
+
 }  // namespace
 
 }  // namespace golh
@@ -334,6 +410,7 @@ void gol_batch_destroy(gol_batch* b)
     if (b->until) (void)hipFree(b->until);
     if (b->rules) (void)hipFree(b->rules);
     if (b->trace) (void)hipFree(b->trace);
+    if (b->record) (void)hipFree(b->record);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -606,6 +683,77 @@ gol_status gol_batch_step_trace(gol_batch* b, uint64_t generations, uint32_t eve
         HIP_TRY(hipMemcpy2DAsync(live, sample_stride * sizeof(uint32_t), b->trace, rowb, rowb,
                                  plan.samples, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+gol_status gol_batch_step_record_device(gol_batch* b, uint64_t generations, uint32_t every,
+                                        uint64_t first, uint64_t count, uint64_t* frames,
+                                        uint64_t sample_stride_words,
+                                        uint64_t field_stride_words, uint64_t row_stride_words,
+                                        gol_batch_record* out)
+{
+    gol_batch_trace_plan plan;
+    GOL_TRY(record_check(b, generations, every, first, count, frames, sample_stride_words,
+                         field_stride_words, row_stride_words, out, &plan));
+    HIP_TRY(hipSetDevice(b->device));
+    return record_run(b, plan, every, first, count, frames, sample_stride_words,
+                      field_stride_words, row_stride_words, out);
+}
+
+gol_status gol_batch_step_record(gol_batch* b, uint64_t generations, uint32_t every,
+                                 uint64_t first, uint64_t count, uint64_t* frames,
+                                 uint64_t sample_stride_words, uint64_t field_stride_words,
+                                 uint64_t row_stride_words, gol_batch_record* out)
+{
+    gol_batch_trace_plan plan;
+    GOL_TRY(record_check(b, generations, every, first, count, frames, sample_stride_words,
+                         field_stride_words, row_stride_words, out, &plan));
+    HIP_TRY(hipSetDevice(b->device));
+    // (samples * count * h * wq <= samples * sample_stride_words, which record_check has
+    // bounded)
+    const uint64_t fw = b->h * b->wq, sw = count * fw;
+    const size_t words = (size_t)(plan.samples * sw);
+    const bool compact = row_stride_words == b->wq && field_stride_words == fw &&
+                         sample_stride_words == sw;
+    // a caller's image with gaps is filled row by row from a host copy of the compact one,
+    // which is taken before anything is stepped too
+    uint64_t* host = nullptr;
+    if (words > 0 && !compact) {
+        host = new (std::nothrow) uint64_t[words];
+        if (!host) return fail(GOL_ENOMEM, "the host copy of the batch's record buffer");
+    }
+    struct Free {
+        uint64_t* p;
+        ~Free() { delete[] p; }
+    } free_host{host};
+    if (b->record_words < words) {
+        if (b->record) {
+            HIP_TRY(hipStreamSynchronize(b->stream));
+            (void)hipFree(b->record);
+            b->record = nullptr;
+            b->record_words = 0;
+        }
+        if (hipMalloc(&b->record, words * sizeof(uint64_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            b->record = nullptr;
+            return fail(GOL_ENOMEM, "the batch's record buffer");
+        }
+        b->record_words = words;
+    }
+    GOL_TRY(record_run(b, plan, every, first, count, b->record, sw, fw, b->wq, out));
+    if (words == 0) return GOL_OK;
+    HIP_TRY(hipMemcpyAsync(compact ? frames : host, b->record, words * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (!compact) {
+        const uint64_t* src = host;
+        for (uint64_t s = 0; s < plan.samples; ++s)
+            for (uint64_t j = 0; j < count; ++j)
+                for (uint64_t r = 0; r < b->h; ++r, src += b->wq)
+                    std::memcpy(frames + s * sample_stride_words + j * field_stride_words +
+                                    r * row_stride_words,
+                                src, b->wq * sizeof(uint64_t));
+    }
     return GOL_OK;
 }
 

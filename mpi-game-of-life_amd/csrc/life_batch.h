@@ -262,9 +262,9 @@ __device__ __forceinline__ LaneRule batch_lane_rule(const uint32_t* rules, int64
     return LaneRule{word & 0x1FFu, (word >> 16) & 0x1FFu};
 }
 
-// (life_batch_until.h's batch_until_run and life_batch_trace.h's batch_trace_run repeat the
-// lane setup and the row load below line for line, so that this kernel compiles as it did:
-// change all three together)
+// (life_batch_until.h's batch_until_run, life_batch_trace.h's batch_trace_run and
+// life_batch_record.h's batch_record_run repeat the lane setup and the row load below line
+// for line, so that this kernel compiles as it did: change all four together)
 // `rules`: RULE_LANE's table (life_batch_rules.h), unused by every other rule kind.
 template <int R, int RULE, bool TORUS, bool MULTI>
 __device__ __forceinline__ void batch_run(const BatchArgs& a, int64_t wave, int lane,

@@ -9,6 +9,7 @@
 #include "life_batch_until.h"
 #include "life_batch_rules.h"
 #include "life_batch_trace.h"
+#include "life_batch_record.h"
 
 namespace gol {
 
@@ -104,6 +105,38 @@ hipError_t launch_batch_trace_rules(const BatchTraceRuleArgs& rt, int rows, hipS
     case 16: return launch_batch_trace_rules_rows<16>(rt, s);
     case 32: return launch_batch_trace_rules_rows<32>(rt, s);
     case 64: return launch_batch_trace_rules_rows<64>(rt, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern template hipError_t launch_batch_record_rows<8>(const BatchRecordArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_record_rows<16>(const BatchRecordArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_record_rows<32>(const BatchRecordArgs&, RuleKind, hipStream_t);
+extern template hipError_t launch_batch_record_rows<64>(const BatchRecordArgs&, RuleKind, hipStream_t);
+
+hipError_t launch_batch_record(const BatchRecordArgs& t, int rows, RuleKind rule, hipStream_t s)
+{
+    switch (rows) {
+    case 8: return launch_batch_record_rows<8>(t, rule, s);
+    case 16: return launch_batch_record_rows<16>(t, rule, s);
+    case 32: return launch_batch_record_rows<32>(t, rule, s);
+    case 64: return launch_batch_record_rows<64>(t, rule, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+extern template hipError_t launch_batch_record_rules_rows<8>(const BatchRecordRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_record_rules_rows<16>(const BatchRecordRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_record_rules_rows<32>(const BatchRecordRuleArgs&, hipStream_t);
+extern template hipError_t launch_batch_record_rules_rows<64>(const BatchRecordRuleArgs&, hipStream_t);
+
+hipError_t launch_batch_record_rules(const BatchRecordRuleArgs& rt, int rows, hipStream_t s)
+{
+    switch (rows) {
+    case 8: return launch_batch_record_rules_rows<8>(rt, s);
+    case 16: return launch_batch_record_rules_rows<16>(rt, s);
+    case 32: return launch_batch_record_rules_rows<32>(rt, s);
+    case 64: return launch_batch_record_rules_rows<64>(rt, s);
     default: return hipErrorInvalidValue;
     }
 }

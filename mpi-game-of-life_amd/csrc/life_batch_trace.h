@@ -109,7 +109,8 @@ __device__ __forceinline__ void batch_trace_run(const BatchTraceArgs& t, int64_t
                                                 const uint32_t* rules = nullptr)
 {
     const BatchArgs& a = t.a;
-    // (lane setup and row load: batch_run's, line for line)
+    // (lane setup and row load: batch_run's, line for line; life_batch_record.h's
+    // batch_record_run repeats them and the interval loop below: change all four together)
     const int32_t h = a.h;
     const int lpf = 1 << a.lpf_shift;
     const int q = lane & (lpf - 1);

@@ -116,7 +116,8 @@ __device__ __forceinline__ void batch_until_run(const BatchUntilArgs& u, int64_t
                                                 const uint32_t* rules = nullptr)
 {
     const BatchArgs& a = u.a;
-    // (lane setup: batch_run's, line for line)
+    // (lane setup: batch_run's, line for line, as in life_batch_trace.h and
+    // life_batch_record.h: change all four together)
     const int32_t h = a.h;
     const int lpf = 1 << a.lpf_shift;
     const int q = lane & (lpf - 1);
